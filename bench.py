@@ -2,7 +2,16 @@
 """bench.py -- device-resident batched CRC32C over 4 KiB blocks on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(value, ms_per_step and the timed region's own roofline fraction).
+`--dump-outputs DIR` also writes the last timed step's CRCs (DIR/crc32c.npy,
+float64, one per block; the inputs are the same seeded stream in every run).
+Everything else below -- verification against the goldens, the diagnostic
+passes, the cfg5 leg, the CPU baseline, the end-to-end and shim legs -- runs
+only with `--full`.
 
 Without a torch.distributed launcher (no WORLD_SIZE in the environment),
 `--gpus N` > 1 makes this process start the N ranks itself (one child process
@@ -23,7 +32,7 @@ No data-path collective: every block's CRC is independent, so shards never
 exchange bytes; only the timing max and a verification digest cross ranks
 (outside the timed region).
 
-The JSON line adds
+The JSON line adds (cfg5 and cpu_baseline with --full only)
   roofline     -- dominant kernel: algorithmic bytes per launch (4096+4 B per
                   block) / its average launch duration in the timed region
                   (HIP events on the launch stream around the K launches / K),
@@ -67,6 +76,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=1000)  # ~67 ms: past the ~30 ms ramp of a sustained load (profiles/r04_clocks_cfg2.jsonl)
     ap.add_argument("--config", choices=["cfg2", "cfg5"], default="cfg2")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: verify the CRCs against the goldens, the untimed diagnostic passes "
+                         "(dispatch events, isolated launches, sustained, read ceiling), the config-5 leg, the CPU "
+                         "baseline and the end-to-end leg; the options below shape those legs and need --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's CRCs to DIR/crc32c.npy (float64)")
     ap.add_argument("--blocks", type=int, default=None, help="override blocks per GPU (cfg2)")
     ap.add_argument("--cpu-seconds", type=float, default=6.0,
                     help="target seconds per CPU-baseline leg (all-core and 1-thread)")
@@ -466,69 +481,18 @@ def _cfg5_traffic(n_local: int):
         return None
 
 
-def main():
-    args = parse()
-    from nvlevelz_amd import launch  # (loads nothing: safe before the ranks exist)
-    rc = launch.main_or_spawn(args.gpus, __file__, sys.argv[1:])
-    if rc is not None:  # launcher-less N > 1: this process only waited for its N ranks
-        sys.exit(rc)
-    import torch
-    import torch.distributed as dist
+def load_golden() -> dict:
+    with open(os.path.join(ROOT, "tests", "golden", "configs.json")) as f:
+        return json.load(f)
 
+
+def verify_first_step(args, out, res, golden: dict, rank: int, N: int, n_local: int, total: int, red_dev) -> dict:
+    """--full: the first step's CRCs (`out` on the device, `res` the same on
+    the host) against the reference-built goldens (tests/golden/configs.json).
+    Rank 0's report; with N > 1 every rank takes part in the collectives."""
     from nvlevelz_amd import crc32c, shard
 
-    re_ = launch.rank_env()
-    world, rank, local = re_["world"], re_["rank"], re_["local_rank"]
-    if world != args.gpus:
-        print(f"[bench] --gpus {args.gpus} but WORLD_SIZE={world}: running {world} rank(s)", file=sys.stderr)
-        args.gpus = world
-    # NVL_BENCH_BACKEND=gloo rehearses the N-rank path on fewer GPUs (ranks
-    # share devices round-robin); the default is RCCL with one GPU per rank.
-    backend = os.environ.get("NVL_BENCH_BACKEND", "nccl")
-    ndev = torch.cuda.device_count()
-    dev = torch.device("cuda", local % ndev if backend == "gloo" else local)
-    torch.cuda.set_device(dev)
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if backend == "gloo":
-            dist.init_process_group("gloo")
-        else:
-            dist.init_process_group("nccl", device_id=dev)  # RCCL; timing/verification only
-    red_dev = torch.device("cpu") if backend == "gloo" else dev
-    crc32c.init(dev.index)
-
-    N = world
-    if args.config == "cfg2":
-        n_local = args.blocks or 100_000
-        seed = SEED_CFG2
-        workload = (f"cfg2: {n_local} x 4 KiB blocks per GPU (BASELINE config 2 at N=1), device-resident, "
-                    f"stride 4096, round-robin global block ids rank+k*N")
-        scaling = "weak"
-        total = n_local * N
-    else:
-        total = 10_000_000
-        n_local = (total - rank + N - 1) // N
-        seed = SEED_CFG5
-        workload = f"cfg5: 10^7 x 4 KiB blocks total (BASELINE config 5), round-robin over {N} GPU(s)"
-        scaling = "strong"
-
-    buf = torch.empty(n_local * BLOCK, dtype=torch.uint8, device=dev)
-    crc32c.fill_splitmix(buf, n_local, BLOCK, seed, first_block=rank, block_step=N)
-    stream = torch.cuda.current_stream(dev)
-    batch = crc32c.FixedBatch(buf, BLOCK, BLOCK, n_local, stream=stream)  # validated once
-    out = batch.out
-    step = batch.launch  # one C call per step; the host stays ahead of the GPU
-
-    step()
-    torch.cuda.synchronize()
-
-    # --- verification (untimed, before the warmup: the timed region starts
-    # right after the warmup launches, not after seconds of host-side checks
-    # with the GPU idle) -----------------------------------------------------
     verify = {}
-    res = crc32c.to_u32(out)
-    with open(os.path.join(ROOT, "tests", "golden", "configs.json")) as f:
-        golden = json.load(f)
     union = golden.get("cfg2_union", {}).get(str(N)) if args.config == "cfg2" and n_local == 100_000 else None
     if N > 1 and (args.config == "cfg5" or union):
         # every rank's own digest (cfg2: golden per-rank digests of the
@@ -539,45 +503,37 @@ def main():
         v = shard.verify_shards(out[:n_local].to(red_dev), total, g)
         if rank == 0:
             verify.update(v)
-            verify["crc0_ok"] = int(v["crc0"], 16) == golden[args.config if args.config == "cfg5" else "cfg2"][
-                "crc_first"][0]
+            first = golden[args.config if args.config == "cfg5" else "cfg2"]["crc_first"][0]
+            verify["crc0_ok"] = int(v["crc0"], 16) == first
     elif args.config == "cfg5" or (N == 1 and n_local == 100_000):
         # the CRCs in global order -> digest = Value() of the little-endian
         # CRC array, golden from the reference build
-        # (tests/golden/configs.json)
         g = golden[args.config]
-        allc = res
         if rank == 0:
-            d = crc32c.value(np.ascontiguousarray(allc, dtype="<u4").tobytes())
-            verify.update({"crc0": hex(int(allc[0])), "crc0_ok": int(allc[0]) == g["crc_first"][0],
-                           "crc_last_ok": int(allc[-1]) == g["crc_last"],
-                           "digest": hex(d), "digest_ok": d == g["digest"], "blocks_checked": int(allc.size)})
+            d = crc32c.value(np.ascontiguousarray(res, dtype="<u4").tobytes())
+            verify.update({"crc0": hex(int(res[0])), "crc0_ok": int(res[0]) == g["crc_first"][0],
+                           "crc_last_ok": int(res[-1]) == g["crc_last"],
+                           "digest": hex(d), "digest_ok": d == g["digest"], "blocks_checked": int(res.size)})
     elif rank == 0:
         verify["crc0"] = hex(int(res[0]))
         verify["crc0_ok"] = int(res[0]) == golden["cfg2"]["crc_first"][0]
+    return verify
 
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize()
 
-    # --- timed region ------------------------------------------------------
-    # K back-to-back launches, nothing else enqueued between them.  Two HIP
-    # events on the launch stream bracket the region (interval / K = mean
-    # launch period, gaps included).
-    K = args.steps
-    tw = shard.timed_window(step, K, stream=stream, world=world)
-    elapsed = tw["elapsed_s"]
-    region_ms = tw["period_s"] * K * 1e3
-    # Beside the in-regime figure, two untimed diagnostic passes (K launches
-    # each, after the timed region; tools/rocprof_summary.py splits them off a
-    # rocprofv3 trace of this command by launch order):
-    #  * dispatch events: nvl_crc32c_fixed_dev_timed, whose kernel dispatch
-    #    records its own start/stop events (hipExtLaunchKernel).  Back to back
-    #    these overlap: a dispatch's start stamp is taken while the previous
-    #    kernel still drains, so their mean can exceed the launch period and
-    #    is never used for the roofline;
-    #  * isolated launches: an ordinary event before and after each launch, so
-    #    every launch starts from an idle queue -- what one shim call sees.
+def diagnostic_passes(args, batch, buf, stream, dev, K: int) -> dict:
+    """--full: beside the in-regime figure, untimed diagnostic passes (K
+    launches each, after the timed region; tools/rocprof_summary.py splits
+    them off a rocprofv3 trace of this command by launch order):
+     * dispatch events: nvl_crc32c_fixed_dev_timed, whose kernel dispatch
+       records its own start/stop events (hipExtLaunchKernel).  Back to back
+       these overlap: a dispatch's start stamp is taken while the previous
+       kernel still drains, so their mean can exceed the launch period and
+       is never used for the roofline;
+     * isolated launches: an ordinary event before and after each launch, so
+       every launch starts from an idle queue -- what one shim call sees."""
+    import torch
+
+    step = batch.launch
     kev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * K)]
     for e in kev:
         e.record(stream)  # materialise the HIP events
@@ -650,6 +606,120 @@ def main():
             ip[2 * k + 1].record(stream)
             torch.cuda.synchronize()
         probe["isolated_median_us"] = float(np.median([ip[2 * k].elapsed_time(ip[2 * k + 1]) * 1e3 for k in range(K)]))
+    return {"kern_ms": kern_ms, "iso_ms": iso_ms, "qev_ms": qev_ms, "sus": sus, "probe": probe}
+
+
+DUMP_MAX_VALUES = 3_000_000  # with their indices 16 B each: 48 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(dirname: str, out, rank: int) -> dict:
+    """--dump-outputs: the CRCs the last timed step left in the batch's result
+    tensor (what a caller of nvl_crc32c_fixed_dev receives), one value per
+    block in this rank's local order, as float64 (every u32 is exact in it) in
+    DIR/crc32c.npy (rank 0; rank r > 0 writes crc32c_rank<r>.npy).  A result
+    of more than 3 * 10^6 blocks is cut to a fixed seeded sample of its blocks,
+    whose sorted indices go beside it (crc32c_index.npy)."""
+    from nvlevelz_amd import crc32c
+
+    os.makedirs(dirname, exist_ok=True)
+    crcs = crc32c.to_u32(out)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    files = {}
+    cap = DUMP_MAX_VALUES
+    if crcs.size > cap:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(crcs.size, size=cap, replace=False))
+        crcs = crcs[idx]
+        name = f"crc32c_index{suffix}.npy"
+        np.save(os.path.join(dirname, name), idx.astype(np.float64))
+        files[name] = int(idx.size)
+    name = f"crc32c{suffix}.npy"
+    np.save(os.path.join(dirname, name), crcs.astype(np.float64))
+    files[name] = int(crcs.size)
+    return files
+
+
+def main():
+    args = parse()
+    from nvlevelz_amd import launch  # (loads nothing: safe before the ranks exist)
+    rc = launch.main_or_spawn(args.gpus, __file__, sys.argv[1:])
+    if rc is not None:  # launcher-less N > 1: this process only waited for its N ranks
+        sys.exit(rc)
+    import torch
+    import torch.distributed as dist
+
+    from nvlevelz_amd import crc32c, shard
+
+    re_ = launch.rank_env()
+    world, rank, local = re_["world"], re_["rank"], re_["local_rank"]
+    if world != args.gpus:
+        print(f"[bench] --gpus {args.gpus} but WORLD_SIZE={world}: running {world} rank(s)", file=sys.stderr)
+        args.gpus = world
+    # NVL_BENCH_BACKEND=gloo rehearses the N-rank path on fewer GPUs (ranks
+    # share devices round-robin); the default is RCCL with one GPU per rank.
+    backend = os.environ.get("NVL_BENCH_BACKEND", "nccl")
+    ndev = torch.cuda.device_count()
+    dev = torch.device("cuda", local % ndev if backend == "gloo" else local)
+    torch.cuda.set_device(dev)
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if backend == "gloo":
+            dist.init_process_group("gloo")
+        else:
+            dist.init_process_group("nccl", device_id=dev)  # RCCL; timing/verification only
+    red_dev = torch.device("cpu") if backend == "gloo" else dev
+    crc32c.init(dev.index)
+
+    N = world
+    if args.config == "cfg2":
+        n_local = args.blocks or 100_000
+        seed = SEED_CFG2
+        workload = (f"cfg2: {n_local} x 4 KiB blocks per GPU (BASELINE config 2 at N=1), device-resident, "
+                    f"stride 4096, round-robin global block ids rank+k*N")
+        scaling = "weak"
+        total = n_local * N
+    else:
+        total = 10_000_000
+        n_local = (total - rank + N - 1) // N
+        seed = SEED_CFG5
+        workload = f"cfg5: 10^7 x 4 KiB blocks total (BASELINE config 5), round-robin over {N} GPU(s)"
+        scaling = "strong"
+
+    buf = torch.empty(n_local * BLOCK, dtype=torch.uint8, device=dev)
+    crc32c.fill_splitmix(buf, n_local, BLOCK, seed, first_block=rank, block_step=N)
+    stream = torch.cuda.current_stream(dev)
+    batch = crc32c.FixedBatch(buf, BLOCK, BLOCK, n_local, stream=stream)  # validated once
+    out = batch.out
+    step = batch.launch  # one C call per step; the host stays ahead of the GPU
+
+    step()
+    torch.cuda.synchronize()
+
+    # --- verification (--full only; untimed, before the warmup: the timed
+    # region starts right after the warmup launches, not after seconds of
+    # host-side checks with the GPU idle).  A plain run compares nothing with
+    # a reference: its CRCs leave through --dump-outputs instead. ------------
+    verify = None
+    if args.full:
+        res = crc32c.to_u32(out)
+        golden = load_golden()
+        verify = verify_first_step(args, out, res, golden, rank, N, n_local, total, red_dev)
+
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize()
+
+    # --- timed region ------------------------------------------------------
+    # K back-to-back launches, nothing else enqueued between them.  Two HIP
+    # events on the launch stream bracket the region (interval / K = mean
+    # launch period, gaps included).
+    K = args.steps
+    tw = shard.timed_window(step, K, stream=stream, world=world)
+    elapsed = tw["elapsed_s"]
+    region_ms = tw["period_s"] * K * 1e3
+    dumped = None
+    if args.dump_outputs:  # the last timed step's results, before anything else writes `out`
+        dumped = dump_outputs(args.dump_outputs, out, rank)
+    diag = diagnostic_passes(args, batch, buf, stream, dev, K) if args.full else None
     # the slowest rank's own window (each rank's elapsed ends at its own
     # synchronize; the closing barrier is timed apart) and every rank's period
     rows = shard.gather_floats([elapsed, tw["period_s"], tw["barrier_after_s"], n_local], red_dev)
@@ -683,18 +753,18 @@ def main():
             traffic = None
 
     c5 = None
-    if args.config == "cfg2" and args.cfg5_steps > 0:  # BASELINE config 5 beside the cfg2 headline (all ranks)
+    if args.full and args.config == "cfg2" and args.cfg5_steps > 0:  # BASELINE config 5 beside cfg2 (all ranks)
         c5 = cfg5_leg(args.cfg5_steps, args.cfg5_warmup, rank, N, dev, red_dev, golden)
 
     cpu = None
     e2e = None
-    if rank == 0 and N == 1 and not args.no_cpu:
+    if args.full and rank == 0 and N == 1 and not args.no_cpu:
         host = buf[:100_000 * BLOCK].cpu().numpy() if n_local > 100_000 else buf.cpu().numpy()
         cpu = cpu_baseline(host, min(n_local, 100_000), args.cpu_seconds, args.cpu_threads)
         chk = cpu.pop("_check")
         verify["cpu_matches_gpu"] = bool(np.array_equal(chk, res[:chk.size]))
         del host
-    if rank == 0 and N == 1 and not args.no_e2e:
+    if args.full and rank == 0 and N == 1 and not args.no_e2e:
         ne = min(n_local, 100_000)
         pinned = torch.empty(ne * BLOCK, dtype=torch.uint8).pin_memory()
         pinned.copy_(buf[:ne * BLOCK].cpu())
@@ -748,21 +818,7 @@ def main():
                                         "nothing else enqueued; an upper bound on the kernel's own time); "
                                         "achieved = alg_bytes / this",
                          "frac_wall": round(frac_wall, 4),
-                         "frac_wall_what": "alg_bytes / ms_per_step (wall clock incl. synchronize) / peak",
-                         "dispatch_event_mean_us": round(float(kern_ms.mean()) * 1e3, 2),
-                         "dispatch_event_what": "untimed diagnostic: start/stop events recorded by each kernel "
-                                                "dispatch (hipExtLaunchKernel), K back-to-back launches; they overlap "
-                                                "the previous kernel's drain, so not used for frac",
-                         "isolated_median_us": round(float(np.median(iso_ms)) * 1e3, 2),
-                         "isolated_frac": round(alg_bytes / (float(np.median(iso_ms)) / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "isolated_what": "untimed diagnostic: ordinary events before and after each launch and a "
-                                          "synchronize after it (every launch starts from an idle queue, as a single "
-                                          "synchronous shim call does); median",
-                         "queued_event_pairs_median_us": round(float(np.median(qev_ms)) * 1e3, 2),
-                         "queued_event_pairs_what": "untimed diagnostic: the same K launches with their event pairs "
-                                                    "queued back to back, no synchronize between them (round 5's "
-                                                    "isolated pass): each launch's start waits on the markers of "
-                                                    "the one before (DESIGN.md section 4)"},
+                         "frac_wall_what": "alg_bytes / ms_per_step (wall clock incl. synchronize) / peak"},
             "timing": {"what": "value = all ranks' blocks x K / the MAX over ranks of each rank's own elapsed "
                                "(from its start after the opening barrier + synchronize to its own synchronize "
                                "after the K launches); the closing barrier is outside it (barrier_after_ms); "
@@ -772,6 +828,27 @@ def main():
             "cpu_baseline": cpu,
             "verify": verify,
         }
+        if dumped:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "values_per_file": dumped, "dtype": "float64",
+                                      "what": "the CRCs of the last timed step, one per block in local order"}
+        sus = probe = None
+        if diag:
+            kern_ms, iso_ms, qev_ms, sus, probe = (diag[k] for k in ("kern_ms", "iso_ms", "qev_ms", "sus", "probe"))
+            line["roofline"].update({
+                "dispatch_event_mean_us": round(float(kern_ms.mean()) * 1e3, 2),
+                "dispatch_event_what": "untimed diagnostic: start/stop events recorded by each kernel dispatch "
+                                       "(hipExtLaunchKernel), K back-to-back launches; they overlap the previous "
+                                       "kernel's drain, so not used for frac",
+                "isolated_median_us": round(float(np.median(iso_ms)) * 1e3, 2),
+                "isolated_frac": round(alg_bytes / (float(np.median(iso_ms)) / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+                "isolated_what": "untimed diagnostic: ordinary events before and after each launch and a "
+                                 "synchronize after it (every launch starts from an idle queue, as a single "
+                                 "synchronous shim call does); median",
+                "queued_event_pairs_median_us": round(float(np.median(qev_ms)) * 1e3, 2),
+                "queued_event_pairs_what": "untimed diagnostic: the same K launches with their event pairs queued "
+                                           "back to back, no synchronize between them (round 5's isolated pass): "
+                                           "each launch's start waits on the markers of the one before (DESIGN.md "
+                                           "section 4)"})
         if sus:
             mp = float(np.mean(sus["segment_period_us"]))
             sus.update({"mean_period_us": round(mp, 2), "frac": round(alg_bytes / (mp * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
@@ -808,7 +885,7 @@ def main():
             line["cfg5"] = c5
         if e2e:
             line["e2e"] = e2e
-        if args.shims and N == 1:
+        if args.full and args.shims and N == 1:
             line["shims"] = shim_bench()
         print(json.dumps(line), flush=True)
     if world > 1:

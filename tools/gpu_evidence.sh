@@ -22,14 +22,14 @@ step() {  # name timeout cmd...
 }
 step pytest 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 400 python bench.py
+step bench 400 python bench.py --full
 step configs 400 python tools/bench_configs.py --configs 2,3,4,v,g,r
 step profc 600 bash tools/diag/prof_configs.sh $TAG cfg3 var4097 rand gen cfg2
 PMC_SET=quick step pmc3 300 bash tools/pmc.sh ${TAG}_cfg3 --config cfg3 --launches 10
 PMC_SET=quick step pmcv 300 bash tools/pmc.sh ${TAG}_var4097 --config var4097 --launches 10
 cd /tmp && export TMPDIR=/tmp
 step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- \
-  python3 $R/bench.py --no-cpu --no-e2e --steps 100 --warmup 20
+  python3 $R/bench.py --full --no-cpu --no-e2e --steps 100 --warmup 20
 step shims 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_shims_$TAG -o run -- \
-  python3 $R/bench.py --shims --no-cpu --no-e2e --steps 20 --warmup 5
+  python3 $R/bench.py --full --shims --no-cpu --no-e2e --steps 20 --warmup 5
 echo "[evidence] done"
