@@ -189,6 +189,26 @@ typedef struct nvl_log_event {
 NVL_API int nvl_log_scan(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events,
                          size_t cap, size_t* n_events, uint32_t flags);
 
+/* nvl_log_scan for a log image already in device memory on `stream`'s device: same
+ * events as nvl_log_scan on the same bytes; the headers are parsed, the CRCs checked
+ * and the events laid out on the GPU, and only the events return.  Synchronous on
+ * `stream`.  events == NULL queries the count. */
+NVL_API int nvl_log_scan_dev(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events,
+                             size_t cap, size_t* n_events, void* stream);
+
+/* The same for a HOST-resident image: the bytes go to HBM once (DMA from the caller's
+ * pages when they lie in a range registered with nvl_crc32c_host_register, else through
+ * the thread's pinned staging), then nvl_log_scan_dev's passes.  The calling thread never
+ * walks the image.  Always the GPU engine; no zero-copy form (the image is read twice). */
+NVL_API int nvl_log_scan_staged(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events,
+                                size_t cap, size_t* n_events);
+
+/* Both process a large image in windows of whole 32 KiB blocks (2048 by default; the
+ * environment variable NVL_LOG_DEV_WINDOW_BLOCKS, read once per process, overrides it)
+ * and fail like every GPU batch: the engine's error, nothing written, no fallback. */
+
+#define NVL_LOG_DEVICE_PARSE 0x800u /* nvl::shims::LogReader: scan through nvl_log_scan_staged */
+
 /* Writer side (replaces the per-fragment crc32c::Extend/Mask of
  * log_writer.cc:93-97): for each header offset, data[off+4..off+7) already
  * holds length and type; writes EncodeFixed32(Mask(Value(data[off+6 ..

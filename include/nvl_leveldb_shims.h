@@ -65,7 +65,8 @@ class LogReader {
   };
 
   // log_reader.h:32-44.  `file` must stay live while the reader is used;
-  // `flags`: 0 = the size policy (nvl_framing_uses_gpu), NVL_FRAMING_HOST / NVL_FRAMING_GPU force an engine.
+  // `flags`: 0 = the size policy (nvl_framing_uses_gpu), NVL_FRAMING_HOST / NVL_FRAMING_GPU force an engine;
+  // NVL_LOG_DEVICE_PARSE: the GPU parses the headers too (nvl_log_scan_staged; forces the GPU).
   LogReader(const char* file, uint64_t file_len, Reporter* reporter, bool checksum, uint64_t initial_offset,
             uint32_t flags = 0)
       : file_(file),
@@ -227,8 +228,20 @@ class LogReader {
     size_t ne = 0;
     const size_t cap = (size_t)(n / kHeader + n / kBlock + 4);  // bound on the event count
     events_.resize(cap);
-    status_ = nvl_log_scan(file_ + block_start, n, block_start, checksum_ ? 1 : 0, events_.data(), cap, &ne, flags_);
+    status_ = ScanImage(file_ + block_start, n, block_start, events_.data(), cap, &ne);
     events_.resize(status_ == NVL_CRC32C_OK ? ne : 0);
+  }
+
+  // The scan of an image or a window.  NVL_LOG_DEVICE_PARSE: the bytes go to
+  // the GPU once and the headers are parsed there too (nvl_log_scan_staged:
+  // always the GPU engine, so together with NVL_FRAMING_HOST an argument
+  // error); otherwise nvl_log_scan under the engine flags.
+  int ScanImage(const char* data, uint64_t n, uint64_t start, nvl_log_event* events, size_t cap, size_t* ne) {
+    if (flags_ & NVL_LOG_DEVICE_PARSE) {
+      if (flags_ & NVL_FRAMING_HOST) return NVL_CRC32C_EINVAL;
+      return nvl_log_scan_staged(data, n, start, checksum_ ? 1 : 0, events, cap, ne);
+    }
+    return nvl_log_scan(data, n, start, checksum_ ? 1 : 0, events, cap, ne, flags_);
   }
 
   // Streaming: read the next window and scan it.  A full window is not the
@@ -258,7 +271,7 @@ class LogReader {
       const size_t cap = (size_t)(parse / kHeader + parse / kBlock + 4);
       events_.resize(cap);
       size_t ne = 0;
-      status_ = nvl_log_scan(win_.data(), parse, start, checksum_ ? 1 : 0, events_.data(), cap, &ne, flags_);
+      status_ = ScanImage(win_.data(), parse, start, events_.data(), cap, &ne);
       events_.resize(status_ == NVL_CRC32C_OK ? ne : 0);
       if (status_ != NVL_CRC32C_OK) return;
       if (!events_.empty() && events_.back().kind == NVL_LOG_EOF) events_.pop_back();

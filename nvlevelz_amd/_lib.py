@@ -75,6 +75,8 @@ SIGNATURES = {
     "nvl_sstable_seal_trailers": (_int, [_vp, _u64, _vp, _sz, _u32]),
     "nvl_sstable_verify_blocks": (_int, [_vp, _u64, _vp, _sz, _vp, _vp, _u32]),
     "nvl_log_scan": (_int, [_vp, _u64, _u64, _int, _vp, _sz, _vp, _u32]),
+    "nvl_log_scan_dev": (_int, [_vp, _u64, _u64, _int, _vp, _sz, _vp, _vp]),
+    "nvl_log_scan_staged": (_int, [_vp, _u64, _u64, _int, _vp, _sz, _vp]),
     "nvl_log_seal": (_int, [_vp, _u64, _vp, _sz, _u32]),
     "nvl_sstable_verify_table": (_int, [_vp, _u64, _vp, _sz, _vp, _vp, _vp, _u32]),
     "nvl_sstable_verify_table_dev": (_int, [_vp, _u64, _vp, _sz, _vp, _vp, _vp, _vp]),
@@ -82,6 +84,7 @@ SIGNATURES = {
 
 FRAMING_HOST = 0x100
 FRAMING_GPU = 0x400
+LOG_DEVICE_PARSE = 0x800  # nvl::shims::LogReader: scan through nvl_log_scan_staged
 BLOCK_OK, BLOCK_TRUNCATED, BLOCK_CHECKSUM_MISMATCH, BLOCK_BAD_TYPE = 0, 1, 2, 3
 LOG_RECORD, LOG_BAD_LENGTH, LOG_CHECKSUM, LOG_ZERO, LOG_EOF = 0, 1, 2, 3, 4
 BLOCK_BAD_HANDLE = 4

@@ -968,6 +968,35 @@ int nvl_crc32c_host_registered(const void* ptr, size_t bytes) {
   return ptr && reg_find(reinterpret_cast<uintptr_t>(ptr), bytes) != g_reg.end() ? 1 : 0;
 }
 
+}  // extern "C"
+
+namespace nvl {
+
+uint8_t* thread_staging(size_t bytes) {
+  t_res.enroll();
+  return static_cast<uint8_t*>(t_res.staging.get(bytes));
+}
+
+bool host_registered(const void* p, uint64_t bytes) { return nvl_crc32c_host_registered(p, bytes) == 1; }
+
+hipError_t host_window_h2d(uint8_t* dst, uint8_t* hst, const uint8_t* src, uint64_t bytes, bool registered,
+                           hipStream_t st) {
+  if (registered)  // DMA from the registered pages
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  // The window goes to the GPU in slices: the staging copy of slice k+1 (a
+  // few host threads for large windows) overlaps the H2D DMA of slice k, so
+  // the call costs max(copy, PCIe) instead of their sum.
+  return stage_h2d(dst, hst, src, bytes, st);
+}
+
+hipError_t wait_host_stream(int device, hipStream_t st, uint64_t bytes, std::chrono::steady_clock::time_point t0) {
+  return wait_host_call(device, st, bytes, t0);
+}
+
+}  // namespace nvl
+
+extern "C" {
+
 int nvl_crc32c_batch_region_host(const void* region, uint64_t region_len, const uint64_t* offsets,
                                  const uint64_t* lengths, const uint32_t* init, uint32_t init_all, uint32_t* out,
                                  uint64_t n, uint32_t flags) {
@@ -1028,14 +1057,7 @@ int nvl_crc32c_batch_region_host(const void* region, uint64_t region_len, const 
   void* dws = reinterpret_cast<uint8_t*>(dout) + align_up(n * 4, 256);
   const uint8_t* dwin = zero_copy ? dsrc : d;
   hipError_t e = hipSuccess;
-  if (reg && !zero_copy && wbytes) {
-    e = hipMemcpyAsync(d, src, wbytes, hipMemcpyHostToDevice, st);  // DMA from the registered pages
-  } else if (!reg) {
-    // The window goes to the GPU in slices: the staging copy of slice k+1 (a
-    // few host threads for large windows) overlaps the H2D DMA of slice k, so
-    // the call costs max(copy, PCIe) instead of their sum.
-    e = stage_h2d(d, hst, src, wbytes, st);
-  }
+  if (!zero_copy) e = host_window_h2d(d, hst, src, wbytes, reg, st);
   uint64_t* hoff = reinterpret_cast<uint64_t*>(hst + meta_off);
   uint64_t* hlen = hoff + n;
   uint32_t* hini = reinterpret_cast<uint32_t*>(hlen + n);

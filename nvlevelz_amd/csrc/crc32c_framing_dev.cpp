@@ -3,11 +3,16 @@
 // (include/nvl_framing.h).  The table logic is crc32c_framing.cpp's
 // verify_table_core; this file supplies the device-side source (HIP), so the
 // host framing code stays free of HIP calls (tests/native/fuzz_framing.cc
-// builds it under ASan without a GPU).
+// builds it under ASan without a GPU).  Also nvl_log_scan_dev /
+// nvl_log_scan_staged: the log scan with its header parse, CRC check and
+// replay on the GPU (kernels: crc32c_log_dev.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <chrono>
 #include <vector>
 
 #include "crc32c_framing_core.h"
@@ -330,10 +335,197 @@ int table_fast(const uint8_t* f, uint64_t len, nvl_table_block* blocks, size_t c
   return NVL_CRC32C_OK;
 }
 
+// ---- device-resident log scan (kernels: crc32c_log_dev.hip) ----------------
+
+constexpr uint64_t kLogBlk = NVL_LOG_BLOCK_SIZE;
+// Blocks per window: 2048 (64 MiB of log).  A window's workspace is bounded
+// (the position slab 18.3 MiB; 100-byte records: ~0.63 M candidates, 13 MiB
+// of batch metadata, 20 MiB of events) whatever the file's size, a host image
+// is staged window by window through a pinned buffer of that size, and one
+// window's counts fit the kernels' 32-bit sums with room (at most 65536).
+constexpr uint64_t kLogWindowBlocks = 2048, kLogWindowBlocksMax = 65536;
+
+// NVL_LOG_DEV_WINDOW_BLOCKS (read once): the window size, for tests of the
+// window seams.
+uint64_t log_window_blocks() {
+  static const uint64_t v = [] {
+    const char* e = getenv("NVL_LOG_DEV_WINDOW_BLOCKS");
+    if (!e || !*e) return kLogWindowBlocks;
+    char* end = nullptr;
+    const unsigned long long x = strtoull(e, &end, 0);
+    if (!end || *end != '\0' || x == 0) return kLogWindowBlocks;
+    return x > kLogWindowBlocksMax ? kLogWindowBlocksMax : (uint64_t)x;
+  }();
+  return v;
+}
+
+// Device workspace of one window of nblk blocks (wlen bytes) with n candidates
+// and room for evcap events, after the staged image (host images only; 4 KiB
+// of slack, the region pass reads whole pages):
+//   [info nblk x 16][cnt, base, nemit, ebase: (nblk + 1) x 4 each][cut nblk x 4]
+//   [slab nblk x 4682 x 2]  |  [off n x 8][len n x 8][crc n x 4][region workspace][events evcap x 32]
+// i.e. 0.286 x the image bytes + 36 bytes per block + 20 bytes and the region
+// workspace (32 bytes) per candidate + 32 bytes per event.
+struct LogWs {
+  size_t info, cnt, base, nemit, ebase, cut, slab, off, len, crc, region, events, total;
+  size_t region_bytes;
+};
+LogWs log_ws(size_t image_bytes, uint64_t nblk, uint64_t wlen, uint64_t n, uint64_t evcap) {
+  LogWs w;
+  const size_t s4 = up256((nblk + 1) * 4);
+  w.info = image_bytes;
+  w.cnt = w.info + up256(nblk * sizeof(dev::LogBlockInfo));
+  w.base = w.cnt + s4;
+  w.nemit = w.base + s4;
+  w.ebase = w.nemit + s4;
+  w.cut = w.ebase + s4;
+  w.slab = w.cut + s4;
+  w.off = w.slab + up256(nblk * dev::kLogSlab * sizeof(uint16_t));
+  w.len = w.off + up256(n * 8);
+  w.crc = w.len + up256(n * 8);
+  w.region = w.crc + up256(n * 4);
+  w.region_bytes = region_ws_bytes(wlen, n ? n : 1);
+  w.events = w.region + up256(w.region_bytes);
+  w.total = w.events + up256(evcap * sizeof(nvl_log_event)) + 256;
+  return w;
+}
+
+// nvl_log_scan_dev / nvl_log_scan_staged.  The image is dimg (device) or
+// himg (host: each window is staged into the workspace first).  Per window:
+// parse, scan, [the candidate count comes back], expand, the region CRC pass,
+// verdict, scan, emit, [the event count and the events come back].
+int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uint64_t start, int checksum,
+                     nvl_log_event* events, size_t cap, size_t* n_events, hipStream_t st, int dev) {
+  const auto t_call = std::chrono::steady_clock::now();
+  thread_local uint64_t cand_hint = 0;  // the last window's candidates: sizes the next workspace in one go
+  const uint64_t W = log_window_blocks(), NB = len / kLogBlk + 1;  // (the last block is the short one, maybe empty)
+  const bool registered = himg && len && host_registered(himg, len);
+  size_t ne = 0, dev_max = 0, pin_max = 0;  // (a call's requests never shrink: the per-thread buffers stay put)
+  auto fail = [&](int rc) {
+    (void)hipStreamSynchronize(st);  // the workspace is the thread's: nothing may still use it
+    return rc;
+  };
+  auto wait = [&](uint64_t moved) {
+    return himg ? wait_host_stream(dev, st, moved, t_call) : hipStreamSynchronize(st);
+  };
+  for (uint64_t wb = 0; wb < NB; wb += W) {
+    const uint64_t nblk = NB - wb < W ? NB - wb : W;
+    const uint64_t wb0 = wb * kLogBlk;
+    const uint64_t wlen = len - wb0 < nblk * kLogBlk ? len - wb0 : nblk * kLogBlk;
+    const size_t image_bytes = himg ? (size_t)((wlen + 4095) / 4096 * 4096 + 4096) : 0;
+    const uint64_t cap_rem = events && cap > ne ? cap - ne : 0;
+    uint64_t n = std::min<uint64_t>(std::max<uint64_t>(wlen / 64, cand_hint), wlen / NVL_LOG_HEADER_SIZE + 1);
+    uint32_t* pin = nullptr;
+    uint8_t* d = nullptr;
+    const uint8_t* img = nullptr;
+    LogWs L;
+    for (int attempt = 0;; ++attempt) {  // (a second round only when the window holds more candidates than guessed)
+      L = log_ws(image_bytes, nblk, wlen, n, std::min<uint64_t>(n + nblk + 1, cap_rem));
+      dev_max = std::max(dev_max, L.total);
+      pin_max = std::max(pin_max, 256 + L.total - L.events);
+      d = static_cast<uint8_t*>(thread_table_device(dev, dev_max));
+      pin = static_cast<uint32_t*>(thread_table_pinned(pin_max));
+      if (!d || !pin) return fail(NVL_CRC32C_EHIP);
+      img = dimg ? dimg + wb0 : d;
+      if (himg) {
+        uint8_t* hst = registered ? nullptr : thread_staging(wlen ? wlen : 1);
+        if (!registered && !hst) return fail(NVL_CRC32C_EHIP);
+        if (host_window_h2d(d, hst, himg + wb0, wlen, registered, st) != hipSuccess) return fail(NVL_CRC32C_EHIP);
+      }
+      uint32_t* base = reinterpret_cast<uint32_t*>(d + L.base);
+      if (launch_log_parse(img, wlen, (uint32_t)nblk, reinterpret_cast<uint16_t*>(d + L.slab),
+                           reinterpret_cast<dev::LogBlockInfo*>(d + L.info), reinterpret_cast<uint32_t*>(d + L.cnt),
+                           st) != hipSuccess ||
+          launch_log_scan(reinterpret_cast<uint32_t*>(d + L.cnt), base, (uint32_t)nblk, st) != hipSuccess ||
+          hipMemcpyAsync(pin, base + nblk, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+          wait(himg ? wlen : 0) != hipSuccess)
+        return fail(NVL_CRC32C_EHIP);
+      const uint64_t found = pin[0];
+      if (found <= n || attempt) {
+        if (found > n) return fail(NVL_CRC32C_EHIP);  // (cannot happen: the second round was sized by the count)
+        n = found;
+        break;
+      }
+      n = found;
+    }
+    cand_hint = n;
+    const uint64_t evcap = std::min<uint64_t>(n + nblk + 1, cap_rem);
+    const uint16_t* slab = reinterpret_cast<uint16_t*>(d + L.slab);
+    const dev::LogBlockInfo* info = reinterpret_cast<dev::LogBlockInfo*>(d + L.info);
+    const uint32_t* base = reinterpret_cast<uint32_t*>(d + L.base);
+    uint32_t* crc = reinterpret_cast<uint32_t*>(d + L.crc);
+    uint32_t* cut = reinterpret_cast<uint32_t*>(d + L.cut);
+    uint32_t* nemit = reinterpret_cast<uint32_t*>(d + L.nemit);
+    uint32_t* ebase = reinterpret_cast<uint32_t*>(d + L.ebase);
+    nvl_log_event* dev_events = reinterpret_cast<nvl_log_event*>(d + L.events);
+    const bool crc_pass = checksum && n > 0;
+    if (crc_pass) {
+      uint64_t* off = reinterpret_cast<uint64_t*>(d + L.off);
+      uint64_t* ln = reinterpret_cast<uint64_t*>(d + L.len);
+      if (launch_log_expand(slab, info, base, (uint32_t)nblk, off, ln, st) != hipSuccess) return fail(NVL_CRC32C_EHIP);
+      const int rc = nvl_crc32c_region_dev(img, wlen, off, ln, nullptr, 0, crc, n, NVL_CRC32C_FLAG_REGION_SHAPED,
+                                           d + L.region, L.region_bytes, st);
+      if (rc != NVL_CRC32C_OK) return fail(rc);
+    }
+    if (launch_log_verdict(img, slab, info, base, crc, crc_pass ? 1 : 0, (uint32_t)nblk, cut, nemit, st) !=
+            hipSuccess ||
+        launch_log_scan(nemit, ebase, (uint32_t)nblk, st) != hipSuccess ||
+        (evcap && launch_log_emit(img, start + wb0, slab, info, cut, ebase, (uint32_t)nblk, dev_events, evcap, st) !=
+                      hipSuccess) ||
+        hipMemcpyAsync(pin, ebase + nblk, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (evcap && hipMemcpyAsync(reinterpret_cast<uint8_t*>(pin) + 256, dev_events, evcap * sizeof(nvl_log_event),
+                                 hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        wait(0) != hipSuccess)
+      return fail(NVL_CRC32C_EHIP);
+    const uint64_t got = pin[0];
+    const uint64_t take = std::min<uint64_t>(got, evcap);
+    if (take) memcpy(events + ne, reinterpret_cast<uint8_t*>(pin) + 256, take * sizeof(nvl_log_event));
+    ne += got;
+  }
+  *n_events = ne;
+  if (events && ne > cap) return NVL_CRC32C_ENOSPC;
+  return NVL_CRC32C_OK;
+}
+
 }  // namespace
 }  // namespace nvl
 
 extern "C" {
+
+int nvl_log_scan_dev(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events, size_t cap,
+                     size_t* n_events, void* stream) {
+  if (n_events) *n_events = 0;
+  if ((!data && len) || !n_events || (start % nvl::kLogBlk) != 0) return NVL_CRC32C_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int dev = -1;
+  if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0) {
+    (void)hipGetLastError();
+    return NVL_CRC32C_ENODEV;
+  }
+  const int rc = nvl_crc32c_init(dev);
+  if (rc != NVL_CRC32C_OK) return rc;
+  return nvl::log_scan_windows(static_cast<const uint8_t*>(data), nullptr, len, start, checksum, events, cap,
+                               n_events, st, dev);
+}
+
+int nvl_log_scan_staged(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events,
+                        size_t cap, size_t* n_events) {
+  if (n_events) *n_events = 0;
+  if ((!data && len) || !n_events || (start % nvl::kLogBlk) != 0) return NVL_CRC32C_EINVAL;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
+    (void)hipGetLastError();
+    return NVL_CRC32C_ENODEV;
+  }
+  const int rc = nvl_crc32c_init(dev);
+  if (rc != NVL_CRC32C_OK) return rc;
+  hipStream_t st = nullptr;
+  hipEvent_t ea = nullptr, eb = nullptr;
+  if (!nvl::thread_table_aux(dev, &st, &ea, &eb)) return NVL_CRC32C_EHIP;
+  static const uint8_t kNone = 0;  // (an empty image: a host pointer the driver never reads)
+  return nvl::log_scan_windows(nullptr, data ? static_cast<const uint8_t*>(data) : &kNone, len, start, checksum,
+                               events, cap, n_events, st, dev);
+}
 
 int nvl_sstable_verify_table_dev(const void* file, uint64_t file_len, nvl_table_block* blocks, size_t cap,
                                  size_t* n_blocks, uint32_t* table_status, uint64_t* n_bad, void* stream) {

@@ -1,13 +1,15 @@
 // nvlevelz_amd/csrc/crc32c_internal.h -- internal interfaces between the
 // C-ABI layer (crc32c_capi.cpp) and the kernel launchers (crc32c_fixed.hip,
 // crc32c_batch.hip, crc32c_region.hip, crc32c_misc.hip,
-// crc32c_scan.hip).  Not installed; not part of the ABI.
+// crc32c_scan.hip, crc32c_table_dev.hip, crc32c_log_dev.hip).  Not installed;
+// not part of the ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <chrono>
 
 #include "nvl_framing.h"
 
@@ -168,6 +170,49 @@ hipError_t launch_table_verdicts(const void* file, const uint64_t* boff, const u
 void* thread_table_device(int device, size_t bytes);
 void* thread_table_pinned(size_t bytes);
 bool thread_table_aux(int device, hipStream_t* side, hipEvent_t* ev_a, hipEvent_t* ev_b);
+
+// The H2D of a host-resident window, shared by the host entries
+// (nvl_crc32c_batch_region_host, nvl_log_scan_staged): thread_staging is the
+// calling thread's pinned staging buffer, grown to `bytes`; host_window_h2d
+// queues src[0, bytes) -> dst (device) on st, as a DMA from the caller's own
+// pages when they lie in a registered range (`registered`), else through hst
+// slice by slice (the copy of slice k + 1 overlaps the DMA of slice k);
+// host_registered: [p, p + bytes) lies inside one registration;
+// wait_host_stream ends such a call: it waits for st without spinning the
+// calling core when the call moved `bytes` >= 4 MiB since t0.
+uint8_t* thread_staging(size_t bytes);
+bool host_registered(const void* p, uint64_t bytes);
+hipError_t host_window_h2d(uint8_t* dst, uint8_t* hst, const uint8_t* src, uint64_t bytes, bool registered,
+                           hipStream_t st);
+hipError_t wait_host_stream(int device, hipStream_t st, uint64_t bytes, std::chrono::steady_clock::time_point t0);
+
+// nvl_log_scan_dev's kernels (crc32c_log_dev.hip), in stream order: parse
+// (one wave per 32 KiB block: count, closing event and the candidates'
+// positions, kLogSlab u16 per block), scan (out[0..n] = exclusive prefix sums
+// and the total of in[0..n)), expand (the candidates as region batch slots at
+// base[blk] + k), verdict (cut[blk] = first CRC mismatch or count, nemit[blk]
+// = events emitted), emit (the events of block blk from ebase[blk], those
+// below evcap only; `start` = file offset of data[0]).
+namespace dev {
+constexpr uint32_t kLogSlab = 4682;  // a block holds at most 4681 records of 7 bytes
+struct LogBlockInfo {
+  uint32_t count;       // candidate records
+  uint32_t close_kind;  // NVL_LOG_BAD_LENGTH / ZERO / EOF, or 0xFFFFFFFF: none (trailer skipped)
+  uint32_t close_pos;   // where the walk stopped (in the block): the closing event's place
+  uint32_t m;           // block bytes (< 32768: the short last block)
+};
+}  // namespace dev
+hipError_t launch_log_parse(const void* data, uint64_t len, uint32_t nblk, uint16_t* slab, dev::LogBlockInfo* info,
+                            uint32_t* cnt, hipStream_t st);
+hipError_t launch_log_scan(const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t st);
+hipError_t launch_log_expand(const uint16_t* slab, const dev::LogBlockInfo* info, const uint32_t* base, uint32_t nblk,
+                             uint64_t* off, uint64_t* len1, hipStream_t st);
+hipError_t launch_log_verdict(const void* data, const uint16_t* slab, const dev::LogBlockInfo* info,
+                              const uint32_t* base, const uint32_t* crc, int checksum, uint32_t nblk, uint32_t* cut,
+                              uint32_t* nemit, hipStream_t st);
+hipError_t launch_log_emit(const void* data, uint64_t start, const uint16_t* slab, const dev::LogBlockInfo* info,
+                           const uint32_t* cut, const uint32_t* ebase, uint32_t nblk, nvl_log_event* events,
+                           uint64_t evcap, hipStream_t st);
 
 // Exclusive prefix sum over n u64 (crc32c_scan.hip, hipCUB).
 size_t scan_temp_bytes(uint64_t n);

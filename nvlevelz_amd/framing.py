@@ -193,24 +193,53 @@ LOG_KIND = {_lib.LOG_RECORD: "record", _lib.LOG_BAD_LENGTH: "bad record length",
             _lib.LOG_CHECKSUM: "checksum mismatch", _lib.LOG_ZERO: "zero", _lib.LOG_EOF: "eof"}
 
 
-def log_scan(image: BytesLike, *, start: int = 0, checksum: bool = True,
-             host: Optional[bool] = None) -> List[Tuple[str, int, int, int]]:
-    """ReadPhysicalRecord's outcomes over a log image (nvl_log_scan):
-    [(kind, header_offset, payload_length, type)] ending with ("eof", ...)."""
-    ptr, n, _keep = _ro(image)
+def _log_events(scan, n: int, what: str) -> List[Tuple[str, int, int, int]]:
+    """scan(events, cap, count_ref) -> rc, called until the events fit."""
     cnt = ctypes.c_size_t(0)
     # One scan when the guess fits (records of >= ~256 B on average); a log of
     # tinier records is scanned again with the exact count the first call reported.
     cap = n // 256 + 64
     while True:
         ev = (_lib.LogEvent * cap)()
-        rc = _lib.lib.nvl_log_scan(ptr, n, start, int(checksum), ev, cap, ctypes.byref(cnt), _flags(host))
+        rc = scan(ev, cap, ctypes.byref(cnt))
         if rc == _lib.ENOSPC and cnt.value > cap:
             cap = cnt.value
             continue
-        _check(rc, "log_scan")
+        _check(rc, what)
         break
     return [(LOG_KIND[e.kind], e.offset, e.length, e.type) for e in ev[:cnt.value]]
+
+
+def log_scan(image: BytesLike, *, start: int = 0, checksum: bool = True, host: Optional[bool] = None,
+             device_parse: bool = False) -> List[Tuple[str, int, int, int]]:
+    """ReadPhysicalRecord's outcomes over a log image (nvl_log_scan):
+    [(kind, header_offset, payload_length, type)] ending with ("eof", ...).
+    ``device_parse=True``: the bytes go to the GPU once and the headers are
+    parsed there as well (nvl_log_scan_staged; always the GPU, so not with
+    ``host=True``)."""
+    ptr, n, _keep = _ro(image)
+    if device_parse:
+        if host:
+            raise ValueError("log_scan: device_parse runs on the GPU (host=True contradicts it)")
+        return _log_events(lambda ev, cap, cnt: _lib.lib.nvl_log_scan_staged(ptr, n, start, int(checksum), ev, cap, cnt),
+                           n, "log_scan(device_parse)")
+    return _log_events(lambda ev, cap, cnt: _lib.lib.nvl_log_scan(ptr, n, start, int(checksum), ev, cap, cnt,
+                                                                  _flags(host)), n, "log_scan")
+
+
+def log_scan_dev(image, *, start: int = 0, checksum: bool = True, stream=None) -> List[Tuple[str, int, int, int]]:
+    """log_scan for a log image already in device memory: a contiguous 1-D
+    uint8 torch tensor on the GPU (nvl_log_scan_dev: parsed, checked and
+    replayed there; only the events come back)."""
+    import torch
+    if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.uint8 and image.dim() == 1
+            and image.is_contiguous()):
+        raise TypeError("log_scan_dev: a contiguous 1-D uint8 tensor on the GPU")
+    st_ = torch.cuda.current_stream(image.device).cuda_stream if stream is None else stream
+    n = image.numel()
+    with torch.cuda.device(image.device):
+        return _log_events(lambda ev, cap, cnt: _lib.lib.nvl_log_scan_dev(image.data_ptr(), n, start, int(checksum),
+                                                                          ev, cap, cnt, st_), n, "log_scan_dev")
 
 
 def log_seal(image: Union[bytearray, np.ndarray], header_offsets: Sequence[int], *, host: Optional[bool] = None) -> None:

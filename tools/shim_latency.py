@@ -13,6 +13,10 @@ host CRC, one JSON line per (operation, size, engine):
                readahead window, db/version_set.cc:1308,1329)
   manifest10   nvl_log_seal of a 10-record MANIFEST batch (db/version_set.cc:896-909,
                db/log_writer.cc:84-109)
+  log_scan     (--log-scan 64,1024 only) nvl_log_scan_dev on an HBM-resident sealed log,
+               nvl_log_scan_staged and nvl_log_scan (GPU / host CRC) on the same image in
+               registered host memory, with the calling thread's CPU seconds per GiB, and
+               the parse path beside nvl_crc32c_read_probe (profiles/log_scan_dev.jsonl)
 Sizes: tables of 256 KiB .. 128 MiB (max_file_size is 2 MiB, util/options.cc:24;
 compaction outputs and L0 flushes, db/builder.cc:35-45, db/db_impl.cc:923).
 Wall clock per call (synchronous entry points), median of R calls after 2 warm-ups.
@@ -32,6 +36,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--out", default=None)
 ap.add_argument("--sizes", default="0.25,2,8,32,128", help="table sizes in MiB")
+ap.add_argument("--log-scan", default=None, metavar="MIB,...",
+                help="run only the device log scan legs on sealed logs of these sizes (e.g. 64,1024)")
+ap.add_argument("--log-shapes", default="100B,1KiB,32KiB", help="record shapes of the --log-scan legs")
 a = ap.parse_args()
 out = open(a.out, "w") if a.out else None
 
@@ -64,6 +71,127 @@ torch.cuda.set_device(0)
 rc0 = L.nvl_crc32c_init(0)
 assert rc0 == 0, f"nvl_crc32c_init: {rc0}"
 sptr = torch.cuda.current_stream().cuda_stream
+
+
+def sealed_log(mib, payload, seed=11):
+    """A sealed log image of mib MiB: every 32 KiB block holds records of
+    `payload` bytes and one last record filling the block (a trailer of fewer
+    than 7 bytes stays zero, db/log_writer.cc:45-57); random payloads, headers
+    sealed by nvl_log_seal.  Returns the image (numpy) and its record count."""
+    nblk = int(mib * 2**20) // 32768
+    pos, p = [], 0
+    while 32768 - p >= 7:
+        n = payload if 32768 - p - 7 - payload >= 7 else 32768 - p - 7
+        pos.append((p, n))
+        p += 7 + n
+    rng = np.random.default_rng(seed)
+    img = rng.integers(0, 256, nblk * 32768, dtype=np.uint8)
+    blocks = img.reshape(nblk, 32768)
+    blocks[:, p:] = 0
+    for q, n in pos:
+        blocks[:, q + 4] = n & 0xFF
+        blocks[:, q + 5] = n >> 8
+        blocks[:, q + 6] = 1 if n == payload else 4
+    hdr = (np.arange(nblk, dtype=np.uint64)[:, None] * np.uint64(32768) +
+           np.array([q for q, _ in pos], dtype=np.uint64)[None, :]).ravel()
+    rc = L.nvl_log_seal(img.ctypes.data, img.size, hdr.ctypes.data, hdr.size, GPU)
+    assert rc == 0, rc
+    return img, hdr.size
+
+
+def log_scan_legs(sizes, reps):
+    """nvl_log_scan_dev / nvl_log_scan_staged against nvl_log_scan (unchanged
+    by the device log scan: the parent commit's code) on the same sealed log:
+      (a) dev      the image in HBM (HIP events around the call as well)
+      (b) staged   from registered host memory
+      (c) scan_gpu nvl_log_scan, NVL_FRAMING_GPU, the same registered image
+      (d) scan_host nvl_log_scan, NVL_FRAMING_HOST
+    with the calling thread's CPU seconds per GiB, plus the parse path alone
+    (nvl_log_scan_dev, checksum = 0, count only: parse, scans, verdict) beside
+    nvl_crc32c_read_probe over the same bytes."""
+    for mib in sizes:
+        for payload, shape in ((100, "100B"), (1024, "1KiB"), (32761, "32KiB")):
+            if shape not in a.log_shapes.split(","):
+                continue
+            img, nrec = sealed_log(mib, payload)
+            nbytes = img.size
+            gib = nbytes / 2**30
+            cap = nrec + nbytes // 32768 + 4
+            ev = (_lib.LogEvent * cap)()
+            n = ctypes.c_size_t(0)
+            base = {"log_bytes": nbytes, "records": nrec, "shape": shape}
+            assert L.nvl_crc32c_host_register(img.ctypes.data, nbytes) == 0
+            dimg = torch.from_numpy(img).to("cuda")
+            torch.cuda.synchronize()
+            want = nrec + 1  # every record and the final EOF
+
+            def timed(fn, reps):
+                fn(); fn()
+                wall, cpu = [], []
+                for _ in range(reps):
+                    c0, t0 = time.thread_time(), time.perf_counter()
+                    fn()
+                    wall.append(time.perf_counter() - t0)
+                    cpu.append(time.thread_time() - c0)
+                return float(np.median(wall)), float(np.min(wall)), float(np.median(cpu))
+
+            def check(rc):
+                assert rc == 0 and n.value == want, (rc, n.value, want)
+
+            legs = (
+                ("dev", lambda: check(L.nvl_log_scan_dev(dimg.data_ptr(), nbytes, 0, 1, ev, cap, ctypes.byref(n), sptr))),
+                ("staged", lambda: check(L.nvl_log_scan_staged(img.ctypes.data, nbytes, 0, 1, ev, cap, ctypes.byref(n)))),
+                ("scan_gpu", lambda: check(L.nvl_log_scan(img.ctypes.data, nbytes, 0, 1, ev, cap, ctypes.byref(n), GPU))),
+                ("scan_host", lambda: check(L.nvl_log_scan(img.ctypes.data, nbytes, 0, 1, ev, cap, ctypes.byref(n), HOST))),
+            )
+            for name, fn in legs:
+                r = reps if mib <= 64 else max(3, reps // 3)
+                t, tmin, cpu = timed(fn, r)
+                d = dict(base, op="log_scan", leg=name, ms=round(t * 1e3, 3), min_ms=round(tmin * 1e3, 3),
+                         GiBps=round(gib / t, 2), cpu_s_per_GiB=round(cpu / gib, 4), reps=r)
+                if name == "dev":  # HIP events around the device work of one call
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ts = []
+                    for _ in range(r):
+                        e0.record()
+                        fn()
+                        e1.record()
+                        e1.synchronize()
+                        ts.append(e0.elapsed_time(e1))
+                    d["event_ms"] = round(float(np.median(ts)), 3)
+                emit(d)
+            # the parse path alone beside a plain read of the same bytes
+            sink = torch.zeros(64, dtype=torch.int32, device="cuda")
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+            def ev_time(fn, reps):
+                fn(); fn()
+                ts = []
+                for _ in range(reps):
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                return float(np.median(ts))
+
+            def parse_only():
+                rc = L.nvl_log_scan_dev(dimg.data_ptr(), nbytes, 0, 0, None, 0, ctypes.byref(n), sptr)
+                assert rc == 0 and n.value == want, (rc, n.value)
+            tp = ev_time(parse_only, reps)
+            tr = ev_time(lambda: L.nvl_crc32c_read_probe(dimg.data_ptr(), nbytes, sink.data_ptr(), sptr), reps)
+            emit(dict(base, op="log_parse_path", ms=round(tp, 3), GiBps=round(gib / (tp / 1e3), 1),
+                      read_probe_ms=round(tr, 3), read_probe_GiBps=round(gib / (tr / 1e3), 1),
+                      what="nvl_log_scan_dev, checksum = 0, count only: the parse kernel, both scans, the verdict "
+                           "kernel and two host round trips per 64 MiB window (the parse kernel alone was not timed)"))
+            assert L.nvl_crc32c_host_unregister(img.ctypes.data) == 0
+            del dimg
+
+
+if a.log_scan:
+    log_scan_legs([float(x) for x in a.log_scan.split(",")], a.reps)
+    sys.exit(0)
+
 for mib in [float(x) for x in a.sizes.split(",")]:
     nblocks = max(1, int(mib * 2**20 / 4101))
     img = bench.build_table_image(nblocks)
