@@ -13,6 +13,7 @@
 
 #include "crc32c_framing_core.h"
 #include "crc32c_internal.h"
+#include "crc32c_log_core.h"
 #include "crc32c_math.h"
 #include "nvl_framing.h"
 
@@ -87,18 +88,6 @@ int value_many(const uint8_t* region, uint64_t region_len, const std::vector<uin
   }
   return nvl_crc32c_batch_region_host(region, region_len, off.data(), len.data(), nullptr, 0, crc->data(), n, 0);
 }
-
-constexpr uint64_t kLogBlock = NVL_LOG_BLOCK_SIZE;
-constexpr uint64_t kLogHeader = NVL_LOG_HEADER_SIZE;
-
-// One block's speculative parse: every candidate record is assumed to pass
-// its checksum; the block's closing event (if any) is what the parse reached
-// under that assumption.
-struct BlockParse {
-  uint64_t start, end;      // file offsets of the block bytes read
-  size_t first, count;      // candidate records: cand[first .. first+count)
-  nvl_log_event closing;    // BAD_LENGTH / ZERO / EOF, or kind = UINT32_MAX (none: trailer skipped)
-};
 
 }  // namespace
 
@@ -236,60 +225,30 @@ int nvl_sstable_verify_blocks(const void* file, uint64_t file_len, const nvl_blo
   return NVL_CRC32C_OK;
 }
 
+// The block rules are crc32c_log_core.h's, the ones the kernels of
+// nvl_log_scan_dev run (crc32c_log_dev.hip); here are the loops around them.
 int nvl_log_scan(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events, size_t cap,
                  size_t* n_events, uint32_t flags) {
-  if (n_events) *n_events = 0;
-  if ((!data && len) || !n_events || (start % kLogBlock) != 0) return NVL_CRC32C_EINVAL;
+  if (!log_scan_args(data, len, start, n_events)) return NVL_CRC32C_EINVAL;
   const uint8_t* d = static_cast<const uint8_t*>(data);
 
-  // Pass 1: speculative parse of every block (ReadPhysicalRecord's header
-  // checks, log_reader.cc:203-252), collecting candidate records.
-  std::vector<BlockParse> blocks;
-  std::vector<nvl_log_event> cand;
+  // Pass 1: every block walked on its own, the candidates' positions kept
+  // block after block in pos and their CRC slots collected.
+  const uint64_t nblk = len / kLogBlk + 1;  // (the last block is the short one, maybe empty)
+  std::vector<LogBlockInfo> info(nblk);
+  std::vector<uint16_t> pos;
   std::vector<uint64_t> coff, clen;
-  uint64_t b0 = 0;
-  while (true) {
-    // log::Reader reads kBlockSize at a time; a short read (incl. 0 bytes)
-    // marks EOF (log_reader.cc:205-218).
-    const uint64_t m = (len - b0) < kLogBlock ? (len - b0) : kLogBlock;
-    const bool eof = m < kLogBlock;
-    BlockParse bp{start + b0, start + b0 + m, cand.size(), 0, nvl_log_event{}};
-    bp.closing.kind = UINT32_MAX;
-    uint64_t pos = 0;
-    while (true) {
-      nvl_log_event e{start + b0 + pos, bp.end, 0u, 0u, 0u, 0u};
-      if (m - pos < kLogHeader) {
-        if (eof) {  // empty, or a truncated header at the end of the file: EOF, not a corruption
-          e.kind = NVL_LOG_EOF;
-          bp.closing = e;
-        }
-        break;  // otherwise the block trailer is skipped
-      }
-      const uint8_t* h = d + b0 + pos;
-      const uint32_t length = (uint32_t)h[4] | ((uint32_t)h[5] << 8);
-      const uint32_t type = h[6];
-      if (kLogHeader + length > m - pos) {
-        e.kind = eof ? NVL_LOG_EOF : NVL_LOG_BAD_LENGTH;  // :234-244
-        bp.closing = e;
-        break;
-      }
-      if (type == 0 && length == 0) {  // :246-252
-        e.kind = NVL_LOG_ZERO;
-        bp.closing = e;
-        break;
-      }
-      e.kind = NVL_LOG_RECORD;
-      e.length = length;
-      e.type = type;
-      cand.push_back(e);
-      coff.push_back(b0 + pos + 6);  // Value(header + 6, 1 + length): type | payload (:256-257)
-      clen.push_back(1u + length);
-      ++bp.count;
-      pos += kLogHeader + length;
+  uint16_t walk[kLogSlab];
+  for (uint64_t b = 0; b < nblk; ++b) {
+    const uint64_t b0 = b * kLogBlk;
+    const LogBlockInfo bi = log_walk_block(d + b0, len - b0 < kLogBlk ? (uint32_t)(len - b0) : kLogBlk, walk);
+    info[b] = bi;
+    pos.insert(pos.end(), walk, walk + bi.count);
+    for (uint32_t k = 0; k < bi.count; ++k) {
+      const LogSlot s = log_slot(bi, walk, k);
+      coff.push_back(b0 + s.off);
+      clen.push_back(s.len);
     }
-    blocks.push_back(bp);
-    if (eof) break;
-    b0 += kLogBlock;
   }
 
   // Pass 2: every candidate's CRC in one batch.
@@ -299,35 +258,24 @@ int nvl_log_scan(const void* data, uint64_t len, uint64_t start, int checksum, n
     if (rc != NVL_CRC32C_OK) return rc;
   }
 
-  // Pass 3: replay in reader order; a block is cut at its first mismatch
-  // (the rest of the buffer is dropped, log_reader.cc:258-266).
-  size_t ne = 0;
-  auto emit = [&](const nvl_log_event& e) {
-    if (events && ne < cap) events[ne] = e;
-    ++ne;
+  // Pass 3: replay in reader order, each block cut at its first mismatch; the
+  // events below cap are written, all are counted.
+  size_t ne = 0, e = 0, c0 = 0;  // events counted / the next one's place / the block's first candidate
+  auto put = [&](const nvl_log_event& x) {
+    if (events && e < cap) events[e] = x;
+    ++e;
   };
-  for (const BlockParse& bp : blocks) {
-    bool cut = false;
-    for (size_t k = bp.first; k < bp.first + bp.count; ++k) {
-      const nvl_log_event& e = cand[k];
-      if (checksum && crc[k] != unmask(load_le32(d + (e.offset - start)))) {
-        nvl_log_event x = e;
-        x.kind = NVL_LOG_CHECKSUM;
-        x.length = 0;
-        x.type = 0;
-        emit(x);
-        cut = true;
-        break;
-      }
-      emit(e);
-    }
-    if (!cut && bp.closing.kind != UINT32_MAX) emit(bp.closing);
-    const bool eof_block = bp.end - bp.start < kLogBlock;
-    if (eof_block && (cut || bp.closing.kind != NVL_LOG_EOF)) {
-      // a drop or zero record emptied the last buffer: the next read finds nothing
-      nvl_log_event x{bp.end, bp.end, 0u, 0u, NVL_LOG_EOF, 0u};
-      emit(x);
-    }
+  for (uint64_t b = 0; b < nblk; ++b) {
+    const LogBlockInfo& bi = info[b];
+    const uint16_t* p = pos.data() + c0;
+    const uint64_t b0 = b * kLogBlk;
+    uint32_t cut = checksum ? 0u : bi.count;
+    while (cut < bi.count && log_crc_ok(d + b0, p, cut, crc[c0 + cut])) ++cut;
+    e = ne;
+    for (uint32_t k = 0; events && k < cut && e < cap; ++k) put(log_record_event(bi, p, k, d + b0, start + b0));
+    log_tail_events(bi, p, cut, start + b0, put);
+    ne += log_emit_count(bi, p, cut);
+    c0 += bi.count;
   }
   *n_events = ne;
   if (events && ne > cap) return NVL_CRC32C_ENOSPC;
@@ -341,9 +289,9 @@ int nvl_log_seal(void* data, uint64_t len, const uint64_t* header_offsets, size_
   std::vector<uint64_t> off(n), ln(n);
   for (size_t i = 0; i < n; ++i) {
     const uint64_t o = header_offsets[i];
-    if (o > len || len - o < kLogHeader) return NVL_CRC32C_EINVAL;
+    if (o > len || len - o < kLogHdr) return NVL_CRC32C_EINVAL;
     const uint64_t length = (uint64_t)d[o + 4] | ((uint64_t)d[o + 5] << 8);
-    if (len - o - kLogHeader < length) return NVL_CRC32C_EINVAL;
+    if (len - o - kLogHdr < length) return NVL_CRC32C_EINVAL;
     off[i] = o + 6;  // type | payload (log_writer.cc:93-94)
     ln[i] = 1 + length;
   }

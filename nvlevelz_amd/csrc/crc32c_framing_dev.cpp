@@ -17,6 +17,7 @@
 
 #include "crc32c_framing_core.h"
 #include "crc32c_internal.h"
+#include "crc32c_log_core.h"
 #include "crc32c_math.h"
 #include "nvl_crc32c.h"
 #include "nvl_framing.h"
@@ -337,7 +338,6 @@ int table_fast(const uint8_t* f, uint64_t len, nvl_table_block* blocks, size_t c
 
 // ---- device-resident log scan (kernels: crc32c_log_dev.hip) ----------------
 
-constexpr uint64_t kLogBlk = NVL_LOG_BLOCK_SIZE;
 // Blocks per window: 2048 (64 MiB of log).  A window's workspace is bounded
 // (the position slab 18.3 MiB; 100-byte records: ~0.63 M candidates, 13 MiB
 // of batch metadata, 20 MiB of events) whatever the file's size, a host image
@@ -374,13 +374,13 @@ LogWs log_ws(size_t image_bytes, uint64_t nblk, uint64_t wlen, uint64_t n, uint6
   LogWs w;
   const size_t s4 = up256((nblk + 1) * 4);
   w.info = image_bytes;
-  w.cnt = w.info + up256(nblk * sizeof(dev::LogBlockInfo));
+  w.cnt = w.info + up256(nblk * sizeof(LogBlockInfo));
   w.base = w.cnt + s4;
   w.nemit = w.base + s4;
   w.ebase = w.nemit + s4;
   w.cut = w.ebase + s4;
   w.slab = w.cut + s4;
-  w.off = w.slab + up256(nblk * dev::kLogSlab * sizeof(uint16_t));
+  w.off = w.slab + up256(nblk * kLogSlab * sizeof(uint16_t));
   w.len = w.off + up256(n * 8);
   w.crc = w.len + up256(n * 8);
   w.region = w.crc + up256(n * 4);
@@ -434,7 +434,7 @@ int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uin
       }
       uint32_t* base = reinterpret_cast<uint32_t*>(d + L.base);
       if (launch_log_parse(img, wlen, (uint32_t)nblk, reinterpret_cast<uint16_t*>(d + L.slab),
-                           reinterpret_cast<dev::LogBlockInfo*>(d + L.info), reinterpret_cast<uint32_t*>(d + L.cnt),
+                           reinterpret_cast<LogBlockInfo*>(d + L.info), reinterpret_cast<uint32_t*>(d + L.cnt),
                            st) != hipSuccess ||
           launch_log_scan(reinterpret_cast<uint32_t*>(d + L.cnt), base, (uint32_t)nblk, st) != hipSuccess ||
           hipMemcpyAsync(pin, base + nblk, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -451,7 +451,7 @@ int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uin
     cand_hint = n;
     const uint64_t evcap = std::min<uint64_t>(n + nblk + 1, cap_rem);
     const uint16_t* slab = reinterpret_cast<uint16_t*>(d + L.slab);
-    const dev::LogBlockInfo* info = reinterpret_cast<dev::LogBlockInfo*>(d + L.info);
+    const LogBlockInfo* info = reinterpret_cast<LogBlockInfo*>(d + L.info);
     const uint32_t* base = reinterpret_cast<uint32_t*>(d + L.base);
     uint32_t* crc = reinterpret_cast<uint32_t*>(d + L.crc);
     uint32_t* cut = reinterpret_cast<uint32_t*>(d + L.cut);
@@ -494,8 +494,7 @@ extern "C" {
 
 int nvl_log_scan_dev(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events, size_t cap,
                      size_t* n_events, void* stream) {
-  if (n_events) *n_events = 0;
-  if ((!data && len) || !n_events || (start % nvl::kLogBlk) != 0) return NVL_CRC32C_EINVAL;
+  if (!nvl::log_scan_args(data, len, start, n_events)) return NVL_CRC32C_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   int dev = -1;
   if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0) {
@@ -510,8 +509,7 @@ int nvl_log_scan_dev(const void* data, uint64_t len, uint64_t start, int checksu
 
 int nvl_log_scan_staged(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events,
                         size_t cap, size_t* n_events) {
-  if (n_events) *n_events = 0;
-  if ((!data && len) || !n_events || (start % nvl::kLogBlk) != 0) return NVL_CRC32C_EINVAL;
+  if (!nvl::log_scan_args(data, len, start, n_events)) return NVL_CRC32C_EINVAL;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
     (void)hipGetLastError();

@@ -192,25 +192,18 @@ hipError_t wait_host_stream(int device, hipStream_t st, uint64_t bytes, std::chr
 // and the total of in[0..n)), expand (the candidates as region batch slots at
 // base[blk] + k), verdict (cut[blk] = first CRC mismatch or count, nemit[blk]
 // = events emitted), emit (the events of block blk from ebase[blk], those
-// below evcap only; `start` = file offset of data[0]).
-namespace dev {
-constexpr uint32_t kLogSlab = 4682;  // a block holds at most 4681 records of 7 bytes
-struct LogBlockInfo {
-  uint32_t count;       // candidate records
-  uint32_t close_kind;  // NVL_LOG_BAD_LENGTH / ZERO / EOF, or 0xFFFFFFFF: none (trailer skipped)
-  uint32_t close_pos;   // where the walk stopped (in the block): the closing event's place
-  uint32_t m;           // block bytes (< 32768: the short last block)
-};
-}  // namespace dev
-hipError_t launch_log_parse(const void* data, uint64_t len, uint32_t nblk, uint16_t* slab, dev::LogBlockInfo* info,
+// below evcap only; `start` = file offset of data[0]).  The block rules,
+// LogBlockInfo and kLogSlab: crc32c_log_core.h, shared with the host scan.
+struct LogBlockInfo;
+hipError_t launch_log_parse(const void* data, uint64_t len, uint32_t nblk, uint16_t* slab, LogBlockInfo* info,
                             uint32_t* cnt, hipStream_t st);
 hipError_t launch_log_scan(const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t st);
-hipError_t launch_log_expand(const uint16_t* slab, const dev::LogBlockInfo* info, const uint32_t* base, uint32_t nblk,
+hipError_t launch_log_expand(const uint16_t* slab, const LogBlockInfo* info, const uint32_t* base, uint32_t nblk,
                              uint64_t* off, uint64_t* len1, hipStream_t st);
-hipError_t launch_log_verdict(const void* data, const uint16_t* slab, const dev::LogBlockInfo* info,
+hipError_t launch_log_verdict(const void* data, const uint16_t* slab, const LogBlockInfo* info,
                               const uint32_t* base, const uint32_t* crc, int checksum, uint32_t nblk, uint32_t* cut,
                               uint32_t* nemit, hipStream_t st);
-hipError_t launch_log_emit(const void* data, uint64_t start, const uint16_t* slab, const dev::LogBlockInfo* info,
+hipError_t launch_log_emit(const void* data, uint64_t start, const uint16_t* slab, const LogBlockInfo* info,
                            const uint32_t* cut, const uint32_t* ebase, uint32_t nblk, nvl_log_event* events,
                            uint64_t evcap, hipStream_t st);
 

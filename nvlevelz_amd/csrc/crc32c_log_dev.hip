@@ -1,31 +1,28 @@
 // nvlevelz_amd/csrc/crc32c_log_dev.hip -- the device side of nvl_log_scan_dev
 // / nvl_log_scan_staged (crc32c_framing_dev.cpp): a log image in HBM is
 // parsed, checked and replayed on the GPU, so only the nvl_log_events return.
-// The three passes of nvl_log_scan (crc32c_framing.cpp) restated as kernels,
-// ordered by kernel boundaries alone (no workgroup ever waits for another):
+// The three passes of nvl_log_scan (crc32c_framing.cpp) as kernels: the block
+// rules are crc32c_log_core.h's, shared with the host scan; here are the
+// thread-parallel loops and the staging, ordered by kernel boundaries alone
+// (no workgroup ever waits for another):
 //
 //   parse    one wave per 32 KiB log block (log::Reader restarts its parse at
 //            every block, db/log_reader.cc:199-218): the block is staged into
 //            LDS with 16-byte loads and one lane walks the record headers
-//            there (ReadPhysicalRecord's header checks, :203-252) -- a hop
-//            in LDS instead of a dependent HBM miss per record.  Per block:
-//            the candidate count, the closing event (BAD_LENGTH / ZERO / EOF
-//            or none) with the position the walk stopped at, and every
+//            there (log_walk_block) -- a hop in LDS instead of a dependent
+//            HBM miss per record.  Per block: a LogBlockInfo and every
 //            candidate's position in the block (u16).
 //   scan     exclusive prefix sum of the per-block counts (one looped
 //            workgroup: there is one element per 32 KiB of log).
 //   expand   the candidates in file order as the offsets[] / lengths[] of
-//            nvl_crc32c_region_dev: b0 + pos + 6 and 1 + length (type |
-//            payload, :256-257); a candidate's length is the distance to the
-//            next position, so the image is not read again.
+//            nvl_crc32c_region_dev (log_slot).
 //   (CRC)    nvl_crc32c_region_dev over the image, NVL_CRC32C_FLAG_REGION_SHAPED:
 //            the candidates are sorted, disjoint, at most 32762 bytes and
 //            inside the image by construction.
-//   verdict  every candidate compares its CRC with Unmask(its header's stored
-//            value); a block is cut at its first mismatch (:258-266) and
-//            counts the events it emits.
+//   verdict  every candidate checks its CRC (log_crc_ok); a block is cut at
+//            its first mismatch and counts the events it emits.
 //   scan     the emitted counts to bases.
-//   emit     the events in reader order (pass 3 of nvl_log_scan).
+//   emit     the events in reader order.
 //
 // Workspace per window of nblk blocks holding n candidates (the formula of
 // crc32c_framing_dev.cpp's log_ws): nblk * (16 + 5 * 4) + 5 * 4 bytes of
@@ -36,16 +33,13 @@
 #include <stdint.h>
 
 #include "crc32c_internal.h"
-#include "crc32c_math.h"
+#include "crc32c_log_core.h"
 #include "nvl_framing.h"
 
 namespace nvl {
 namespace dev {
 namespace {
 
-constexpr uint32_t kLogBlk = NVL_LOG_BLOCK_SIZE;
-constexpr uint32_t kLogHdr = NVL_LOG_HEADER_SIZE;
-constexpr uint32_t kNoClose = 0xFFFFFFFFu;  // LogBlockInfo::close_kind: the block trailer was skipped
 constexpr uint32_t kScanThreads = 1024;
 
 // One 16-byte piece of the image at g, bytes outside [lo, hi) read as zero
@@ -60,10 +54,6 @@ __device__ __forceinline__ uint4 load_edge16(const uint8_t* g, const uint8_t* lo
     w[i >> 2] |= b << (8u * (i & 3u));
   }
   return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__device__ __forceinline__ uint32_t ld_le32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
 }  // namespace
@@ -94,31 +84,10 @@ __global__ __launch_bounds__(64) void crc32c_log_parse(const uint8_t* __restrict
   }
   __syncthreads();
   if (lane != 0) return;
-  // pass 1 of nvl_log_scan (crc32c_framing.cpp), one block
-  const bool eof = m < kLogBlk;
-  uint16_t* s = slab + (uint64_t)blk * kLogSlab;
-  uint32_t pos = 0, count = 0, kind = kNoClose;
-  while (true) {
-    if (m - pos < kLogHdr) {
-      if (eof) kind = NVL_LOG_EOF;  // empty, or a truncated header at the end of the file
-      break;                        // otherwise the block trailer is skipped
-    }
-    const uint8_t* h = lds + a + pos;
-    const uint32_t length = (uint32_t)h[4] | ((uint32_t)h[5] << 8);
-    const uint32_t type = h[6];
-    if (kLogHdr + length > m - pos) {
-      kind = eof ? NVL_LOG_EOF : NVL_LOG_BAD_LENGTH;
-      break;
-    }
-    if (type == 0 && length == 0) {
-      kind = NVL_LOG_ZERO;
-      break;
-    }
-    s[count++] = (uint16_t)pos;  // pos <= 32761, count <= 4681: every record takes 7 bytes at least
-    pos += kLogHdr + length;
-  }
-  info[blk] = LogBlockInfo{count, kind, pos, m};
-  cnt[blk] = count;
+  // one lane walks the headers in LDS; the block's kLogSlab positions hold any block's candidates
+  const LogBlockInfo bi = log_walk_block(lds + a, m, slab + (uint64_t)blk * kLogSlab);
+  info[blk] = bi;
+  cnt[blk] = bi.count;
 }
 
 // out[i] = in[0] + ... + in[i - 1] for i = 0..n (out[n]: the total), one
@@ -156,15 +125,15 @@ __global__ __launch_bounds__(256) void crc32c_log_expand(const uint16_t* __restr
   const uint16_t* s = slab + (uint64_t)blk * kLogSlab;
   const uint64_t b0 = (uint64_t)blk * kLogBlk, k0 = base[blk];
   for (uint32_t k = threadIdx.x; k < bi.count; k += blockDim.x) {
-    const uint32_t pos = s[k], nxt = k + 1u < bi.count ? (uint32_t)s[k + 1u] : bi.close_pos;
-    off[k0 + k] = b0 + pos + 6u;
-    ln[k0 + k] = nxt - pos - 6u;  // 1 + length
+    const LogSlot c = log_slot(bi, s, k);
+    off[k0 + k] = b0 + c.off;
+    ln[k0 + k] = c.len;
   }
 }
 
 // cut[blk] = the block's first candidate whose CRC does not match its header
 // (count: none; nothing is compared when checksum = 0), nemit[blk] = the
-// events the block emits (pass 3 of nvl_log_scan).
+// events the block emits.
 __global__ __launch_bounds__(256) void crc32c_log_verdict(const uint8_t* __restrict__ data,
                                                           const uint16_t* __restrict__ slab,
                                                           const LogBlockInfo* __restrict__ info,
@@ -174,24 +143,19 @@ __global__ __launch_bounds__(256) void crc32c_log_verdict(const uint8_t* __restr
   __shared__ uint32_t s_cut;
   const uint32_t blk = blockIdx.x;
   const LogBlockInfo bi = info[blk];
+  const uint16_t* s = slab + (uint64_t)blk * kLogSlab;
   if (threadIdx.x == 0) s_cut = bi.count;
   __syncthreads();
   if (checksum) {
-    const uint16_t* s = slab + (uint64_t)blk * kLogSlab;
     const uint8_t* b = data + (uint64_t)blk * kLogBlk;
     const uint64_t k0 = base[blk];
     for (uint32_t k = threadIdx.x; k < bi.count; k += blockDim.x)
-      if (crc[k0 + k] != nvl::unmask(ld_le32(b + s[k]))) atomicMin(&s_cut, k);
+      if (!log_crc_ok(b, s, k, crc[k0 + k])) atomicMin(&s_cut, k);
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  const uint32_t c = s_cut;
-  const bool is_cut = c < bi.count;
-  uint32_t e = is_cut ? c + 1u : bi.count + (bi.close_kind != kNoClose ? 1u : 0u);
-  // a drop or zero record emptied the last buffer: the next read finds nothing
-  if (bi.m < kLogBlk && (is_cut || bi.close_kind != NVL_LOG_EOF)) ++e;
-  cut[blk] = c;
-  nemit[blk] = e;
+  cut[blk] = s_cut;
+  nemit[blk] = log_emit_count(bi, s, s_cut);
 }
 
 // The events of block blockIdx.x at events[ebase[blk] ...), those below evcap
@@ -205,31 +169,25 @@ __global__ __launch_bounds__(256) void crc32c_log_emit(const uint8_t* __restrict
   const uint32_t blk = blockIdx.x;
   const LogBlockInfo bi = info[blk];
   const uint16_t* s = slab + (uint64_t)blk * kLogSlab;
-  const uint64_t b0 = (uint64_t)blk * kLogBlk, f0 = start + b0, block_end = f0 + bi.m;
+  const uint64_t b0 = (uint64_t)blk * kLogBlk, f0 = start + b0;
   const uint32_t c = cut[blk];
   const uint32_t nrec = c < bi.count ? c : bi.count;
   const uint64_t e0 = ebase[blk];
   for (uint32_t k = threadIdx.x; k < nrec; k += blockDim.x) {
     if (e0 + k >= evcap) break;
-    const uint32_t pos = s[k], nxt = k + 1u < bi.count ? (uint32_t)s[k + 1u] : bi.close_pos;
-    events[e0 + k] = nvl_log_event{f0 + pos, block_end, nxt - pos - kLogHdr, data[b0 + pos + 6u], NVL_LOG_RECORD, 0u};
+    events[e0 + k] = log_record_event(bi, s, k, data + b0, f0);
   }
   if (threadIdx.x != 0) return;
   uint64_t e = e0 + nrec;
-  if (c < bi.count) {
-    if (e < evcap) events[e] = nvl_log_event{f0 + s[c], block_end, 0u, 0u, NVL_LOG_CHECKSUM, 0u};
+  log_tail_events(bi, s, c, f0, [&](const nvl_log_event& x) {
+    if (e < evcap) events[e] = x;
     ++e;
-  } else if (bi.close_kind != kNoClose) {
-    if (e < evcap) events[e] = nvl_log_event{f0 + bi.close_pos, block_end, 0u, 0u, bi.close_kind, 0u};
-    ++e;
-  }
-  if (bi.m < kLogBlk && (c < bi.count || bi.close_kind != NVL_LOG_EOF) && e < evcap)
-    events[e] = nvl_log_event{block_end, block_end, 0u, 0u, NVL_LOG_EOF, 0u};
+  });
 }
 
 }  // namespace dev
 
-hipError_t launch_log_parse(const void* data, uint64_t len, uint32_t nblk, uint16_t* slab, dev::LogBlockInfo* info,
+hipError_t launch_log_parse(const void* data, uint64_t len, uint32_t nblk, uint16_t* slab, LogBlockInfo* info,
                             uint32_t* cnt, hipStream_t st) {
   if (nblk == 0 || (uint64_t)(nblk - 1u) * NVL_LOG_BLOCK_SIZE > len) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dev::crc32c_log_parse, dim3(nblk), dim3(64), 0, st, static_cast<const uint8_t*>(data), len, slab,
@@ -242,13 +200,13 @@ hipError_t launch_log_scan(const uint32_t* in, uint32_t* out, uint32_t n, hipStr
   return hipGetLastError();
 }
 
-hipError_t launch_log_expand(const uint16_t* slab, const dev::LogBlockInfo* info, const uint32_t* base, uint32_t nblk,
+hipError_t launch_log_expand(const uint16_t* slab, const LogBlockInfo* info, const uint32_t* base, uint32_t nblk,
                              uint64_t* off, uint64_t* len1, hipStream_t st) {
   hipLaunchKernelGGL(dev::crc32c_log_expand, dim3(nblk), dim3(256), 0, st, slab, info, base, off, len1);
   return hipGetLastError();
 }
 
-hipError_t launch_log_verdict(const void* data, const uint16_t* slab, const dev::LogBlockInfo* info,
+hipError_t launch_log_verdict(const void* data, const uint16_t* slab, const LogBlockInfo* info,
                               const uint32_t* base, const uint32_t* crc, int checksum, uint32_t nblk, uint32_t* cut,
                               uint32_t* nemit, hipStream_t st) {
   hipLaunchKernelGGL(dev::crc32c_log_verdict, dim3(nblk), dim3(256), 0, st, static_cast<const uint8_t*>(data), slab,
@@ -256,7 +214,7 @@ hipError_t launch_log_verdict(const void* data, const uint16_t* slab, const dev:
   return hipGetLastError();
 }
 
-hipError_t launch_log_emit(const void* data, uint64_t start, const uint16_t* slab, const dev::LogBlockInfo* info,
+hipError_t launch_log_emit(const void* data, uint64_t start, const uint16_t* slab, const LogBlockInfo* info,
                            const uint32_t* cut, const uint32_t* ebase, uint32_t nblk, nvl_log_event* events,
                            uint64_t evcap, hipStream_t st) {
   hipLaunchKernelGGL(dev::crc32c_log_emit, dim3(nblk), dim3(256), 0, st, static_cast<const uint8_t*>(data), start, slab,

@@ -6,11 +6,16 @@ Parity anchors:
 * tests/golden/log_cases.json -- the REFERENCE's own log::Reader traces
   (see tests/test_framing.py): every case through shims::LogReader with
   NVL_LOG_DEVICE_PARSE, whole image and streamed in windows of 1 and 3 blocks;
-* nvl_log_scan(..., NVL_FRAMING_HOST), unchanged host code that the existing
-  tests pin to the reference: both new entry points must return exactly its
-  events (every field, `reserved` included) on the fixtures' images, on
-  synthetic edge images, on a seeded header fuzz, and with the window size
-  forced to 1 and 3 blocks (NVL_LOG_DEV_WINDOW_BLOCKS, one child process each).
+* nvl_log_scan(..., NVL_FRAMING_HOST): both device entry points must return
+  exactly its events (every field, `reserved` included) on the fixtures'
+  images, on synthetic edge images, on a seeded header fuzz, and with the
+  window size forced to 1 and 3 blocks (NVL_LOG_DEV_WINDOW_BLOCKS, one child
+  process each).  The host scan and the kernels run the same block rules
+  (nvlevelz_amd/csrc/crc32c_log_core.h), so this comparison alone would pass
+  a rule bug shared by both; the host side is anchored without a GPU: to the
+  reference's traces by tests/test_framing.py, and on the edge and fuzz
+  images of this module to the events recorded before the rules were shared
+  (tests/test_log_scan_golden.py, tests/golden/log_scan_events.json).
 
 Run as a script (the window children): `python tests/test_log_scan_dev.py`
 checks the edge images and 20 fuzz seeds under the environment's window size.
