@@ -209,6 +209,65 @@ NVL_API int nvl_log_scan_staged(const void* data, uint64_t len, uint64_t start, 
 
 #define NVL_LOG_DEVICE_PARSE 0x800u /* nvl::shims::LogReader: scan through nvl_log_scan_staged */
 
+/* ---- logical records (log::Reader::ReadRecord, db/log_reader.cc:62-175) ---- */
+
+/* The reason of a corruption report, with the reference's text and what its byte count is. */
+#define NVL_LOG_REASON_BAD_LENGTH 1      /* "bad record length"                      bytes = block_end - offset */
+#define NVL_LOG_REASON_CHECKSUM 2        /* "checksum mismatch"                      same */
+#define NVL_LOG_REASON_PARTIAL_1 3       /* "partial record without end(1)"          bytes = scratch size */
+#define NVL_LOG_REASON_PARTIAL_2 4       /* "partial record without end(2)" */
+#define NVL_LOG_REASON_MISSING_START_1 5 /* "missing start of fragmented record(1)"  bytes = fragment size */
+#define NVL_LOG_REASON_MISSING_START_2 6 /* "missing start of fragmented record(2)" */
+#define NVL_LOG_REASON_IN_MIDDLE 7       /* "error in middle of record"              bytes = scratch size */
+#define NVL_LOG_REASON_UNKNOWN_TYPE 8    /* "unknown record type %u"                 bytes = fragment + scratch */
+
+typedef struct nvl_log_record { /* one ReadRecord() that returned true */
+  uint64_t offset;              /* LastRecordOffset(): header of its FULL / FIRST fragment */
+  uint64_t payload;             /* where its bytes start in the payload buffer */
+  uint64_t length;              /* its bytes: the sum of its fragments */
+  uint32_t fragments;
+  uint32_t reports_before;      /* reports issued before this record was returned */
+} nvl_log_record;
+typedef struct nvl_log_report {
+  uint64_t bytes;
+  uint32_t reason; /* NVL_LOG_REASON_* */
+  uint32_t type;   /* NVL_LOG_REASON_UNKNOWN_TYPE: the %u */
+} nvl_log_report;
+typedef struct nvl_log_read_totals {
+  uint64_t n_records, n_reports, payload_bytes;
+} nvl_log_read_totals;
+
+#define NVL_LOG_PAYLOAD_HOST 0x1000u /* nvl_log_read_dev: `payload` is host memory (gathered on the GPU, one D2H) */
+
+/* Read a log image the way log::Reader::ReadRecord does, from initial_offset
+ * (SkipToInitialBlock included; data[0] is file offset 0): the logical records
+ * -- FIRST / MIDDLE / LAST fragments joined, FULL passed through -- with their
+ * bytes packed in `payload` without gaps (records[k + 1].payload ==
+ * records[k].payload + records[k].length), and the corruption reports that
+ * pass the reader's initial_offset filter.  Records and reports are in reader
+ * order; report r was issued before record k iff r < records[k].reports_before,
+ * and the reports from the last record's reports_before on follow it.
+ * payload == records == reports == NULL queries *totals.  Too small a cap:
+ * NVL_CRC32C_ENOSPC with exact totals, output contents unspecified; these
+ * always suffice: payload_cap = len, rec_cap = len / 7 + 1, rep_cap = len / 7
+ * + len / 32768 + 2.  The physical scan is nvl_log_scan under `flags` (the
+ * size policy, NVL_FRAMING_HOST or NVL_FRAMING_GPU); the record rules then
+ * run on the calling thread. */
+NVL_API int nvl_log_read(const void* data, uint64_t len, uint64_t initial_offset, int checksum, void* payload,
+                         uint64_t payload_cap, nvl_log_record* records, size_t rec_cap, nvl_log_report* reports,
+                         size_t rep_cap, nvl_log_read_totals* totals, uint32_t flags);
+
+/* The same for a log image in device memory on `stream`'s device: the scan of
+ * nvl_log_scan_dev, then the record rules as prefix scans over its events and
+ * a gather of every delivered fragment into `payload`, all on the GPU.
+ * `payload` is device memory, or with NVL_LOG_PAYLOAD_HOST (the only flag)
+ * host memory filled by one copy; `records` and `reports` are host arrays.
+ * Same results as nvl_log_read on the same bytes, whatever the window size;
+ * synchronous on `stream`; an engine error is returned, with no fallback. */
+NVL_API int nvl_log_read_dev(const void* data, uint64_t len, uint64_t initial_offset, int checksum, void* payload,
+                             uint64_t payload_cap, nvl_log_record* records, size_t rec_cap, nvl_log_report* reports,
+                             size_t rep_cap, nvl_log_read_totals* totals, uint32_t flags, void* stream);
+
 /* Writer side (replaces the per-fragment crc32c::Extend/Mask of
  * log_writer.cc:93-97): for each header offset, data[off+4..off+7) already
  * holds length and type; writes EncodeFixed32(Mask(Value(data[off+6 ..

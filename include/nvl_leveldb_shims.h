@@ -6,6 +6,7 @@
 // adapters (Slice, Status, SequentialFile, WritableFile) for a LevelDB tree.
 //
 //   nvl::shims::LogReader   db/log_reader.h:20-120, db/log_reader.cc:17-281
+//   nvl::shims::DeviceLogReader  the same reader over a log image in device memory (HBM)
 //   nvl::shims::LogWriter   db/log_writer.h:18-47, db/log_writer.cc:17-109
 //   nvl::shims::TableFile   TableBuilder::WriteRawBlock table/table_builder.cc:175-193
 //                           + the checks of ReadBlock table/format.cc:65-98
@@ -372,6 +373,118 @@ class LogReader {
   bool src_eof_ = false, has_fail_ = false, skip_failed_ = false;
   uint64_t fail_end_ = 0;
   std::string fail_msg_;
+};
+
+// ---------------------------------------------------------------------------
+// log::Reader over a log image that lies in device memory (HBM): the first
+// ReadRecord has the GPU scan the image, join the fragments and gather the
+// records' bytes (nvl_log_read_dev with NVL_LOG_PAYLOAD_HOST: the records, the
+// reports and the payload come back, the image does not), then the records
+// and the corruption reports are replayed in the reader's order.  Same
+// surface as LogReader; no HIP here: `stream` is a hipStream_t passed through.
+class DeviceLogReader {
+ public:
+  typedef LogReader::Reporter Reporter;
+
+  // `dev_image` (byte 0 = file offset 0) must stay live until the first ReadRecord returned.
+  DeviceLogReader(const void* dev_image, uint64_t file_len, void* stream, Reporter* reporter, bool checksum,
+                  uint64_t initial_offset)
+      : image_(dev_image),
+        file_len_(file_len),
+        stream_(stream),
+        reporter_(reporter),
+        checksum_(checksum),
+        initial_offset_(initial_offset) {}
+
+  // log_reader.h:46-52.  False at the end of the input, or when the device
+  // call failed (status() != NVL_CRC32C_OK; nothing is returned then).  The
+  // record's bytes stay valid as long as the reader; *scratch is not used.
+  bool ReadRecord(const char** data, size_t* size, std::string* scratch) {
+    if (!read_) Read();
+    scratch->clear();
+    *data = "";
+    *size = 0;
+    if (status_ != NVL_CRC32C_OK) return false;
+    const bool more = next_ < records_.size();
+    const size_t upto = more ? records_[next_].reports_before : reports_.size();
+    for (; next_report_ < upto; ++next_report_) Report(reports_[next_report_]);
+    if (!more) return false;
+    const nvl_log_record& r = records_[next_++];
+    *data = payload_.data() + r.payload;
+    *size = (size_t)r.length;
+    last_record_offset_ = r.offset;
+    return true;
+  }
+
+  template <class Slice>
+  bool ReadRecord(Slice* record, std::string* scratch) {
+    const char* d;
+    size_t n;
+    const bool ok = ReadRecord(&d, &n, scratch);
+    *record = Slice(d, n);
+    return ok;
+  }
+
+  uint64_t LastRecordOffset() const { return last_record_offset_; }
+  int status() const { return status_; }
+
+  // The reference's Status::Corruption text of an nvl_log_report.
+  static std::string ReasonText(const nvl_log_report& r) {
+    switch (r.reason) {
+      case NVL_LOG_REASON_BAD_LENGTH: return "bad record length";
+      case NVL_LOG_REASON_CHECKSUM: return "checksum mismatch";
+      case NVL_LOG_REASON_PARTIAL_1: return "partial record without end(1)";
+      case NVL_LOG_REASON_PARTIAL_2: return "partial record without end(2)";
+      case NVL_LOG_REASON_MISSING_START_1: return "missing start of fragmented record(1)";
+      case NVL_LOG_REASON_MISSING_START_2: return "missing start of fragmented record(2)";
+      case NVL_LOG_REASON_IN_MIDDLE: return "error in middle of record";
+      default: {
+        char buf[40];
+        snprintf(buf, sizeof(buf), "unknown record type %u", (unsigned)r.type);
+        return buf;
+      }
+    }
+  }
+
+ private:
+  // One call when the guess fits (records of >= 64 bytes on average, a report
+  // per 4 KiB); else once more with the exact totals the first call reported.
+  void Read() {
+    read_ = true;
+    nvl_log_read_totals t = {file_len_ / 64 + 16, file_len_ / 4096 + 64, file_len_};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      payload_.resize((size_t)t.payload_bytes);
+      records_.resize((size_t)t.n_records);
+      reports_.resize((size_t)t.n_reports);
+      const uint64_t pcap = t.payload_bytes;
+      const size_t rcap = (size_t)t.n_records, qcap = (size_t)t.n_reports;
+      status_ = nvl_log_read_dev(image_, file_len_, initial_offset_, checksum_ ? 1 : 0, pcap ? &payload_[0] : NULL, pcap,
+                                 records_.data(), rcap, reports_.data(), qcap, &t, NVL_LOG_PAYLOAD_HOST, stream_);
+      if (status_ != NVL_CRC32C_ENOSPC) break;
+    }
+    const bool ok = status_ == NVL_CRC32C_OK;
+    payload_.resize(ok ? (size_t)t.payload_bytes : 0);
+    records_.resize(ok ? (size_t)t.n_records : 0);
+    reports_.resize(ok ? (size_t)t.n_reports : 0);
+  }
+
+  void Report(const nvl_log_report& r) {
+    if (reporter_ != nullptr) reporter_->Corruption((size_t)r.bytes, ReasonText(r).c_str());
+  }
+
+  const void* const image_;
+  const uint64_t file_len_;
+  void* const stream_;
+  Reporter* const reporter_;
+  const bool checksum_;
+  const uint64_t initial_offset_;
+  bool read_ = false;
+  int status_ = NVL_CRC32C_OK;
+  std::string payload_;
+  std::vector<nvl_log_record> records_;
+  std::vector<nvl_log_report> reports_;
+  size_t next_ = 0, next_report_ = 0;
+  uint64_t last_record_offset_ = 0;
 };
 
 // ---------------------------------------------------------------------------

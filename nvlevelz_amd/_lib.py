@@ -78,6 +78,8 @@ SIGNATURES = {
     "nvl_log_scan_dev": (_int, [_vp, _u64, _u64, _int, _vp, _sz, _vp, _vp]),
     "nvl_log_scan_staged": (_int, [_vp, _u64, _u64, _int, _vp, _sz, _vp]),
     "nvl_log_seal": (_int, [_vp, _u64, _vp, _sz, _u32]),
+    "nvl_log_read": (_int, [_vp, _u64, _u64, _int, _vp, _u64, _vp, _sz, _vp, _sz, _vp, _u32]),
+    "nvl_log_read_dev": (_int, [_vp, _u64, _u64, _int, _vp, _u64, _vp, _sz, _vp, _sz, _vp, _u32, _vp]),
     "nvl_sstable_verify_table": (_int, [_vp, _u64, _vp, _sz, _vp, _vp, _vp, _u32]),
     "nvl_sstable_verify_table_dev": (_int, [_vp, _u64, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
@@ -85,6 +87,9 @@ SIGNATURES = {
 FRAMING_HOST = 0x100
 FRAMING_GPU = 0x400
 LOG_DEVICE_PARSE = 0x800  # nvl::shims::LogReader: scan through nvl_log_scan_staged
+LOG_PAYLOAD_HOST = 0x1000  # nvl_log_read_dev: the payload buffer is host memory
+(LOG_REASON_BAD_LENGTH, LOG_REASON_CHECKSUM, LOG_REASON_PARTIAL_1, LOG_REASON_PARTIAL_2, LOG_REASON_MISSING_START_1,
+ LOG_REASON_MISSING_START_2, LOG_REASON_IN_MIDDLE, LOG_REASON_UNKNOWN_TYPE) = range(1, 9)
 BLOCK_OK, BLOCK_TRUNCATED, BLOCK_CHECKSUM_MISMATCH, BLOCK_BAD_TYPE = 0, 1, 2, 3
 LOG_RECORD, LOG_BAD_LENGTH, LOG_CHECKSUM, LOG_ZERO, LOG_EOF = 0, 1, 2, 3, 4
 BLOCK_BAD_HANDLE = 4
@@ -111,6 +116,21 @@ class LogEvent(ctypes.Structure):
     """nvl_log_event (include/nvl_framing.h)."""
     _fields_ = [("offset", _u64), ("block_end", _u64), ("length", _u32), ("type", _u32),
                 ("kind", _u32), ("reserved", _u32)]
+
+
+class LogRecord(ctypes.Structure):
+    """nvl_log_record (include/nvl_framing.h)."""
+    _fields_ = [("offset", _u64), ("payload", _u64), ("length", _u64), ("fragments", _u32), ("reports_before", _u32)]
+
+
+class LogReport(ctypes.Structure):
+    """nvl_log_report (include/nvl_framing.h)."""
+    _fields_ = [("bytes", _u64), ("reason", _u32), ("type", _u32)]
+
+
+class LogReadTotals(ctypes.Structure):
+    """nvl_log_read_totals (include/nvl_framing.h)."""
+    _fields_ = [("n_records", _u64), ("n_reports", _u64), ("payload_bytes", _u64)]
 
 
 def header_symbols(paths: list[str] | None = None) -> list[str]:

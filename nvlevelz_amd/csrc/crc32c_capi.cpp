@@ -541,6 +541,7 @@ struct ThreadRes {
   Staging results;  // pinned landing area of the host entries' results (see wait_host_call)
   HostPipe pipe;
   DevSlab table_dev;      // nvl_sstable_verify_table_dev
+  DevSlab log_read_dev;   // nvl_log_read_dev: the events' table and the record pass (thread_log_read_device)
   Staging table_pinned;
   hipEvent_t table_ev[kMaxDevices][2] = {};
   hipEvent_t wait_ev[kMaxDevices] = {};  // wait_host_call's events
@@ -579,6 +580,8 @@ struct ThreadRes {
     pipe.release();
     if (table_dev.device >= 0) (void)hipSetDevice(table_dev.device);
     table_dev.release();
+    if (log_read_dev.device >= 0) (void)hipSetDevice(log_read_dev.device);
+    log_read_dev.release();
     staging.release();
     results.release();
     table_pinned.release();
@@ -649,6 +652,35 @@ hipError_t wait_host_call(int device, hipStream_t st, uint64_t bytes, Clock::tim
 void* thread_table_device(int device, size_t bytes) {
   t_res.enroll();
   return t_res.table_dev.get(device, bytes);
+}
+
+// Grown to at least twice its size, so a table that grows window by window
+// is copied O(log) times; a buffer nothing is kept of is DevSlab::get's.
+void* thread_log_read_device(int device, size_t bytes, size_t keep, hipStream_t st) {
+  t_res.enroll();
+  DevSlab& s = t_res.log_read_dev;
+  const uint64_t g = g_generation.load(std::memory_order_acquire);
+  if (!keep) return s.get(device, bytes);
+  if (!s.p || s.device != device || s.gen != g) return nullptr;  // (nothing of this call's to keep: shut down meanwhile)
+  if (bytes <= s.cap) return s.p;
+  if (keep > s.cap) return nullptr;
+  const size_t want = std::max(bytes, 2 * s.cap);
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  if (prev != device) (void)hipSetDevice(device);
+  void* q = nullptr;
+  bool ok = hipMalloc(&q, want) == hipSuccess;
+  if (ok) ok = hipMemcpyAsync(q, s.p, keep, hipMemcpyDeviceToDevice, st) == hipSuccess;
+  if (ok) ok = hipStreamSynchronize(st) == hipSuccess;
+  if (ok) {
+    (void)hipFree(s.p);
+    s.p = q;
+    s.cap = want;
+  } else if (q) {
+    (void)hipFree(q);
+  }
+  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+  return ok ? s.p : nullptr;
 }
 
 void* thread_table_pinned(size_t bytes) {

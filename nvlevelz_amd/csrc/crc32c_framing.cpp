@@ -14,6 +14,7 @@
 #include "crc32c_framing_core.h"
 #include "crc32c_internal.h"
 #include "crc32c_log_core.h"
+#include "crc32c_log_read_core.h"
 #include "crc32c_math.h"
 #include "nvl_framing.h"
 
@@ -279,6 +280,64 @@ int nvl_log_scan(const void* data, uint64_t len, uint64_t start, int checksum, n
   }
   *n_events = ne;
   if (events && ne > cap) return NVL_CRC32C_ENOSPC;
+  return NVL_CRC32C_OK;
+}
+
+// The record rules are crc32c_log_read_core.h's, the ones the kernels of
+// nvl_log_read_dev compose (crc32c_log_read.hip); here is the sequential
+// loop: the reader's state, the open record's first event and its scratch
+// size carried from one event to the next.
+int nvl_log_read(const void* data, uint64_t len, uint64_t initial_offset, int checksum, void* payload,
+                 uint64_t payload_cap, nvl_log_record* records, size_t rec_cap, nvl_log_report* reports,
+                 size_t rep_cap, nvl_log_read_totals* totals, uint32_t flags) {
+  bool query = false;
+  if (!log_read_args(data, len, payload, records, reports, totals, &query)) return NVL_CRC32C_EINVAL;
+  if (flags & ~(uint32_t)(NVL_FRAMING_HOST | NVL_FRAMING_GPU)) return NVL_CRC32C_EINVAL;
+  const uint8_t* d = static_cast<const uint8_t*>(data);
+  const uint64_t start = log_read_block_start(initial_offset);
+  if (start >= len) return NVL_CRC32C_OK;  // skipped to (or past) the end: the first read finds nothing
+  const uint64_t n = len - start;
+  std::vector<nvl_log_event> ev((size_t)(n / kLogHdr + n / kLogBlk + 4));
+  size_t ne = 0;
+  const int rc = nvl_log_scan(d + start, n, start, checksum, ev.data(), ev.size(), &ne, flags);
+  if (rc != NVL_CRC32C_OK) return rc;
+
+  uint8_t* out = static_cast<uint8_t*>(payload);
+  uint32_t state = initial_offset > 0 ? kLrResync : kLrIdle;
+  uint64_t scratch = 0, nrec = 0, nrep = 0, bytes = 0;
+  size_t first = 0;  // the open record's FIRST
+  for (size_t i = 0; i < ne; ++i) {
+    const LogReadEvent e = log_read_classify(ev[i], initial_offset);
+    if (e.cls == kLcEof) break;  // ReadRecord returns false for good
+    const LogReadStep s = log_read_step(state, scratch, e, initial_offset);
+    for (uint32_t r = 0; r < s.n_reports; ++r, ++nrep)
+      if (reports && nrep < rep_cap) reports[nrep] = s.rep[r];
+    if (s.record) {
+      const size_t f0 = s.joined ? first : i;
+      const uint64_t length = (s.joined ? scratch : 0) + e.span;
+      if (records && nrec < rec_cap)
+        records[nrec] = nvl_log_record{ev[f0].offset, bytes, length, (uint32_t)(i - f0 + 1), (uint32_t)nrep};
+      if (out && bytes + length <= payload_cap) {
+        uint64_t at = bytes;
+        for (size_t f = f0; f <= i; at += ev[f].length, ++f) memcpy(out + at, d + ev[f].offset + kLogHdr, ev[f].length);
+      }
+      ++nrec;
+      bytes += length;
+    }
+    const uint32_t next = log_read_next(state, e.cls);
+    if (e.cls == kLcFirst) {
+      first = i;
+      scratch = e.span;
+    } else if (next == kLrFrag) {
+      scratch += e.span;  // a MIDDLE of the open record
+    } else {
+      scratch = 0;
+    }
+    state = next;
+  }
+  *totals = nvl_log_read_totals{nrec, nrep, bytes};
+  if (!query && (bytes > (payload ? payload_cap : 0) || nrec > (records ? rec_cap : 0) || nrep > (reports ? rep_cap : 0)))
+    return NVL_CRC32C_ENOSPC;
   return NVL_CRC32C_OK;
 }
 

@@ -5,7 +5,9 @@
 // host framing code stays free of HIP calls (tests/native/fuzz_framing.cc
 // builds it under ASan without a GPU).  Also nvl_log_scan_dev /
 // nvl_log_scan_staged: the log scan with its header parse, CRC check and
-// replay on the GPU (kernels: crc32c_log_dev.hip).
+// replay on the GPU (kernels: crc32c_log_dev.hip), and nvl_log_read_dev: that
+// scan's events joined into ReadRecord's logical records there as well
+// (kernels: crc32c_log_read.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -18,6 +20,7 @@
 #include "crc32c_framing_core.h"
 #include "crc32c_internal.h"
 #include "crc32c_log_core.h"
+#include "crc32c_log_read_core.h"
 #include "crc32c_math.h"
 #include "nvl_crc32c.h"
 #include "nvl_framing.h"
@@ -390,12 +393,42 @@ LogWs log_ws(size_t image_bytes, uint64_t nblk, uint64_t wlen, uint64_t n, uint6
   return w;
 }
 
+constexpr uint64_t kLogReadMaxEvents = 0x7FFFFFFFull;  // nvl_log_read_dev's kernels index events with 32 bits
+constexpr size_t kLogReadHintMax = 256u << 20;          // a call asks for its predecessor's buffer size up to this
+
+// Where a window's events go when they stay in device memory
+// (nvl_log_read_dev): the whole image's table of LogReadEvents in the
+// thread's second device buffer, filled window by window.  take() is called
+// once per window, in order, with the window's events in the window's
+// workspace; the classify kernel it queues runs before the next window
+// reuses that workspace.
+struct LogReadTable {
+  int dev;
+  hipStream_t st;
+  uint64_t initial_offset;
+  size_t hint;  // the thread's last call's buffer: sizes this one's in one go
+  uint64_t n = 0;
+  int take(const nvl_log_event* dev_events, uint64_t got) {
+    if (n + got > kLogReadMaxEvents) return NVL_CRC32C_EINVAL;
+    const size_t need = std::max<size_t>(hint, up256((n + got) * sizeof(LogReadEvent)));
+    LogReadEvent* table =
+        static_cast<LogReadEvent*>(thread_log_read_device(dev, need, n * sizeof(LogReadEvent), st));
+    if (!table) return NVL_CRC32C_EHIP;
+    if (launch_log_read_classify(dev_events, (uint32_t)got, initial_offset, table + n, st) != hipSuccess)
+      return NVL_CRC32C_EHIP;
+    n += got;
+    return NVL_CRC32C_OK;
+  }
+};
+
 // nvl_log_scan_dev / nvl_log_scan_staged.  The image is dimg (device) or
 // himg (host: each window is staged into the workspace first).  Per window:
 // parse, scan, [the candidate count comes back], expand, the region CRC pass,
-// verdict, scan, emit, [the event count and the events come back].
+// verdict, scan, emit, [the event count and the events come back -- or, with
+// a sink, the count alone: every event is emitted and handed to the sink].
 int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uint64_t start, int checksum,
-                     nvl_log_event* events, size_t cap, size_t* n_events, hipStream_t st, int dev) {
+                     nvl_log_event* events, size_t cap, size_t* n_events, hipStream_t st, int dev,
+                     LogReadTable* sink = nullptr) {
   const auto t_call = std::chrono::steady_clock::now();
   thread_local uint64_t cand_hint = 0;  // the last window's candidates: sizes the next workspace in one go
   const uint64_t W = log_window_blocks(), NB = len / kLogBlk + 1;  // (the last block is the short one, maybe empty)
@@ -413,7 +446,7 @@ int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uin
     const uint64_t wb0 = wb * kLogBlk;
     const uint64_t wlen = len - wb0 < nblk * kLogBlk ? len - wb0 : nblk * kLogBlk;
     const size_t image_bytes = himg ? (size_t)((wlen + 4095) / 4096 * 4096 + 4096) : 0;
-    const uint64_t cap_rem = events && cap > ne ? cap - ne : 0;
+    const uint64_t cap_rem = sink ? ~0ull : (events && cap > ne ? cap - ne : 0);
     uint64_t n = std::min<uint64_t>(std::max<uint64_t>(wlen / 64, cand_hint), wlen / NVL_LOG_HEADER_SIZE + 1);
     uint32_t* pin = nullptr;
     uint8_t* d = nullptr;
@@ -422,7 +455,7 @@ int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uin
     for (int attempt = 0;; ++attempt) {  // (a second round only when the window holds more candidates than guessed)
       L = log_ws(image_bytes, nblk, wlen, n, std::min<uint64_t>(n + nblk + 1, cap_rem));
       dev_max = std::max(dev_max, L.total);
-      pin_max = std::max(pin_max, 256 + L.total - L.events);
+      pin_max = std::max(pin_max, 256 + (sink ? 0 : L.total - L.events));  // (a sink's events stay on the device)
       d = static_cast<uint8_t*>(thread_table_device(dev, dev_max));
       pin = static_cast<uint32_t*>(thread_table_pinned(pin_max));
       if (!d || !pin) return fail(NVL_CRC32C_EHIP);
@@ -473,12 +506,18 @@ int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uin
         (evcap && launch_log_emit(img, start + wb0, slab, info, cut, ebase, (uint32_t)nblk, dev_events, evcap, st) !=
                       hipSuccess) ||
         hipMemcpyAsync(pin, ebase + nblk, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (evcap && hipMemcpyAsync(reinterpret_cast<uint8_t*>(pin) + 256, dev_events, evcap * sizeof(nvl_log_event),
-                                 hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (evcap && !sink &&
+         hipMemcpyAsync(reinterpret_cast<uint8_t*>(pin) + 256, dev_events, evcap * sizeof(nvl_log_event),
+                        hipMemcpyDeviceToHost, st) != hipSuccess) ||
         wait(0) != hipSuccess)
       return fail(NVL_CRC32C_EHIP);
     const uint64_t got = pin[0];
-    const uint64_t take = std::min<uint64_t>(got, evcap);
+    if (sink) {
+      if (got > evcap) return fail(NVL_CRC32C_EHIP);  // (cannot happen: a block emits its candidates and a closing event, the last one two)
+      const int rc = sink->take(dev_events, got);
+      if (rc != NVL_CRC32C_OK) return fail(rc);
+    }
+    const uint64_t take = sink ? 0 : std::min<uint64_t>(got, evcap);
     if (take) memcpy(events + ne, reinterpret_cast<uint8_t*>(pin) + 256, take * sizeof(nvl_log_event));
     ne += got;
   }
@@ -487,10 +526,124 @@ int log_scan_windows(const uint8_t* dimg, const uint8_t* himg, uint64_t len, uin
   return NVL_CRC32C_OK;
 }
 
+// ---- device-resident log reader (kernels: crc32c_log_read.hip) -------------
+
+// The thread's second device buffer (thread_log_read_device) during one
+// nvl_log_read_dev of an image with n events (nt = ceil(n / 1024) tiles), R
+// records, P reports and B payload bytes:
+//   [table n x 16]                                       kept across the scan's windows
+//   [tiles A (2 nt + 1) x 16][tiles B (2 nt + 1) x 16]
+//   [state n x 1][first n x 4][scratch n x 8]            after the count: 29 bytes per event + 64 per tile
+//   [records R x 32][rec_first R x 4][reports P x 16]    after the totals came back
+//   [payload B]                                          NVL_LOG_PAYLOAD_HOST only
+// next to the scan's own per-window workspace (log_ws).
+struct LogReadWs {
+  size_t tiles_a, tiles_b, state, first, scratch, pass_end, records, rec_first, reports, payload, total;
+};
+LogReadWs log_read_ws(uint64_t n, uint64_t nrec, uint64_t nrep, uint64_t payload_bytes) {
+  LogReadWs w;
+  const size_t nt = log_read_tiles((uint32_t)n), tiles = up256((2 * nt + 1) * 16);
+  w.tiles_a = up256(n * sizeof(LogReadEvent));
+  w.tiles_b = w.tiles_a + tiles;
+  w.state = w.tiles_b + tiles;
+  w.first = w.state + up256(n);
+  w.scratch = w.first + up256(n * 4);
+  w.pass_end = w.scratch + up256(n * 8);
+  w.records = w.pass_end;
+  w.rec_first = w.records + up256(nrec * sizeof(nvl_log_record));
+  w.reports = w.rec_first + up256(nrec * 4);
+  w.payload = w.reports + up256(nrep * sizeof(nvl_log_report));
+  w.total = w.payload + up256(payload_bytes) + 256;
+  return w;
+}
+
+// nvl_log_read_dev after its argument checks: the scan from the reader's
+// first block with every event kept in the table, the two scans over the
+// table, [the totals come back], emit, gather, [records, reports and, for a
+// host payload, the bytes come back].
+int log_read_dev(const uint8_t* data, uint64_t len, uint64_t initial_offset, int checksum, void* payload,
+                 uint64_t payload_cap, nvl_log_record* records, size_t rec_cap, nvl_log_report* reports,
+                 size_t rep_cap, nvl_log_read_totals* totals, bool query, bool payload_host, hipStream_t st, int dev) {
+  thread_local size_t slab_hint = 0;
+  const uint64_t start = log_read_block_start(initial_offset);
+  LogReadTable sink;
+  sink.dev = dev;
+  sink.st = st;
+  sink.initial_offset = initial_offset;
+  sink.hint = std::min<size_t>(slab_hint, kLogReadHintMax);
+  size_t ne = 0;
+  int rc = log_scan_windows(data + start, nullptr, len - start, start, checksum, nullptr, 0, &ne, st, dev, &sink);
+  if (rc != NVL_CRC32C_OK) return rc;
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(st);  // the buffers are the thread's: nothing may still use them
+    return code;
+  };
+  const uint64_t n = sink.n;
+  if (n == 0) return NVL_CRC32C_OK;
+  LogReadWs L = log_read_ws(n, 0, 0, 0);
+  const size_t keep = n * sizeof(LogReadEvent);
+  uint8_t* d = static_cast<uint8_t*>(thread_log_read_device(dev, std::max(sink.hint, L.total), keep, st));
+  uint64_t* pin = static_cast<uint64_t*>(thread_table_pinned(256));
+  if (!d || !pin) return fail(NVL_CRC32C_EHIP);
+  const uint32_t nt = log_read_tiles((uint32_t)n);
+  const LogReadEvent* table = reinterpret_cast<const LogReadEvent*>(d);
+  if (launch_log_read_count(table, (uint32_t)n, initial_offset > 0 ? kLrResync : kLrIdle, initial_offset,
+                            d + L.tiles_a, d + L.tiles_b, d + L.state, reinterpret_cast<uint32_t*>(d + L.first),
+                            reinterpret_cast<uint64_t*>(d + L.scratch), st) != hipSuccess ||
+      hipMemcpyAsync(pin, d + L.tiles_b + (size_t)2 * nt * 16, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return fail(NVL_CRC32C_EHIP);
+  const uint64_t nrec = (uint32_t)pin[0], nrep = pin[0] >> 32, bytes = pin[1];
+  *totals = nvl_log_read_totals{nrec, nrep, bytes};
+  if (query) return NVL_CRC32C_OK;
+  if (bytes > (payload ? payload_cap : 0) || nrec > (records ? rec_cap : 0) || nrep > (reports ? rep_cap : 0))
+    return NVL_CRC32C_ENOSPC;
+  L = log_read_ws(n, nrec, nrep, payload_host ? bytes : 0);
+  d = static_cast<uint8_t*>(thread_log_read_device(dev, std::max(sink.hint, L.total), L.pass_end, st));
+  if (!d) return fail(NVL_CRC32C_EHIP);
+  slab_hint = L.total;
+  table = reinterpret_cast<const LogReadEvent*>(d);
+  nvl_log_record* drec = reinterpret_cast<nvl_log_record*>(d + L.records);
+  uint32_t* dfirst = reinterpret_cast<uint32_t*>(d + L.rec_first);
+  nvl_log_report* drep = reinterpret_cast<nvl_log_report*>(d + L.reports);
+  const uint64_t* scratch = reinterpret_cast<const uint64_t*>(d + L.scratch);
+  void* dpay = payload_host ? static_cast<void*>(d + L.payload) : payload;
+  if (launch_log_read_emit(table, (uint32_t)n, initial_offset, d + L.tiles_b, d + L.state,
+                           reinterpret_cast<const uint32_t*>(d + L.first), scratch, drec, dfirst, drep,
+                           st) != hipSuccess ||
+      launch_log_read_gather(data, len, table, scratch, drec, dfirst, (uint32_t)nrec, dpay, bytes, st) != hipSuccess ||
+      (nrec && hipMemcpyAsync(records, drec, nrec * sizeof(nvl_log_record), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (nrep && hipMemcpyAsync(reports, drep, nrep * sizeof(nvl_log_report), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (payload_host && bytes && hipMemcpyAsync(payload, dpay, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return fail(NVL_CRC32C_EHIP);
+  return NVL_CRC32C_OK;
+}
+
 }  // namespace
 }  // namespace nvl
 
 extern "C" {
+
+int nvl_log_read_dev(const void* data, uint64_t len, uint64_t initial_offset, int checksum, void* payload,
+                     uint64_t payload_cap, nvl_log_record* records, size_t rec_cap, nvl_log_report* reports,
+                     size_t rep_cap, nvl_log_read_totals* totals, uint32_t flags, void* stream) {
+  bool query = false;
+  if (!nvl::log_read_args(data, len, payload, records, reports, totals, &query)) return NVL_CRC32C_EINVAL;
+  if (flags & ~(uint32_t)NVL_LOG_PAYLOAD_HOST) return NVL_CRC32C_EINVAL;
+  if (nvl::log_read_block_start(initial_offset) >= len) return NVL_CRC32C_OK;  // skipped to (or past) the end
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int dev = -1;
+  if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0) {
+    (void)hipGetLastError();
+    return NVL_CRC32C_ENODEV;
+  }
+  const int rc = nvl_crc32c_init(dev);
+  if (rc != NVL_CRC32C_OK) return rc;
+  return nvl::log_read_dev(static_cast<const uint8_t*>(data), len, initial_offset, checksum, payload, payload_cap,
+                           records, rec_cap, reports, rep_cap, totals, query, (flags & NVL_LOG_PAYLOAD_HOST) != 0, st,
+                           dev);
+}
 
 int nvl_log_scan_dev(const void* data, uint64_t len, uint64_t start, int checksum, nvl_log_event* events, size_t cap,
                      size_t* n_events, void* stream) {

@@ -207,6 +207,35 @@ hipError_t launch_log_emit(const void* data, uint64_t start, const uint16_t* sla
                            const uint32_t* cut, const uint32_t* ebase, uint32_t nblk, nvl_log_event* events,
                            uint64_t evcap, hipStream_t st);
 
+// nvl_log_read_dev's kernels (crc32c_log_read.hip), in stream order: classify
+// (a window's n events into the whole image's table), count (the two scans
+// over the table's n events: per event the reader's state, governing FIRST
+// (index + 1) and scratch size; tiles_a / tiles_b: (2 * log_read_tiles(n) + 1)
+// * 16 bytes each, the last 16 of tiles_b the totals {u32 records, u32
+// reports, u64 payload bytes}), emit (the records, each one's first event and
+// the reports at their places), gather (the records' bytes into payload[0,
+// total), read from data[0, len)).  The record rules and LogReadEvent:
+// crc32c_log_read_core.h, shared with nvl_log_read.
+struct LogReadEvent;
+uint32_t log_read_tiles(uint32_t n);
+hipError_t launch_log_read_classify(const nvl_log_event* events, uint32_t n, uint64_t initial_offset,
+                                    LogReadEvent* table, hipStream_t st);
+hipError_t launch_log_read_count(const LogReadEvent* table, uint32_t n, uint32_t state0, uint64_t initial_offset,
+                                 void* tiles_a, void* tiles_b, uint8_t* state, uint32_t* first, uint64_t* scratch,
+                                 hipStream_t st);
+hipError_t launch_log_read_emit(const LogReadEvent* table, uint32_t n, uint64_t initial_offset, const void* tiles_b,
+                                const uint8_t* state, const uint32_t* first, const uint64_t* scratch,
+                                nvl_log_record* records, uint32_t* rec_first, nvl_log_report* reports,
+                                hipStream_t st);
+hipError_t launch_log_read_gather(const void* data, uint64_t len, const LogReadEvent* table, const uint64_t* scratch,
+                                  const nvl_log_record* records, const uint32_t* rec_first, uint32_t nrec,
+                                  void* payload, uint64_t total, hipStream_t st);
+// The thread's second device buffer (crc32c_capi.cpp), which keeps its first
+// `keep` bytes when it has to grow (copied on st, which is then idle): the
+// whole image's table across the scan's windows, whose own workspace is
+// thread_table_device's.
+void* thread_log_read_device(int device, size_t bytes, size_t keep, hipStream_t st);
+
 // Exclusive prefix sum over n u64 (crc32c_scan.hip, hipCUB).
 size_t scan_temp_bytes(uint64_t n);
 hipError_t exclusive_scan_u64(void* temp, size_t temp_bytes, const uint64_t* in, uint64_t* out, uint64_t n,

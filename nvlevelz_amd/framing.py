@@ -13,7 +13,9 @@ way LevelDB does:
   "file is too short to be an sstable", "not an sstable (bad magic number)",
   "bad block handle", "bad block contents", "bad entry in block";
 * log::Reader::ReadPhysicalRecord, db/log_reader.cc:199-281 -- the per-record
-  outcomes of nvl_log_scan.
+  outcomes of nvl_log_scan;
+* log::Reader::ReadRecord, db/log_reader.cc:62-175 -- the corruption reports
+  of nvl_log_read / nvl_log_read_dev (LOG_REASON_TEXT).
 
 Every function raises :class:`FramingError` on a non-OK return code; there is
 no silent fallback (without a GPU the device mode raises).
@@ -240,6 +242,92 @@ def log_scan_dev(image, *, start: int = 0, checksum: bool = True, stream=None) -
     with torch.cuda.device(image.device):
         return _log_events(lambda ev, cap, cnt: _lib.lib.nvl_log_scan_dev(image.data_ptr(), n, start, int(checksum),
                                                                           ev, cap, cnt, st_), n, "log_scan_dev")
+
+
+LOG_REASON_TEXT = {
+    _lib.LOG_REASON_BAD_LENGTH: "bad record length",
+    _lib.LOG_REASON_CHECKSUM: "checksum mismatch",
+    _lib.LOG_REASON_PARTIAL_1: "partial record without end(1)",
+    _lib.LOG_REASON_PARTIAL_2: "partial record without end(2)",
+    _lib.LOG_REASON_MISSING_START_1: "missing start of fragmented record(1)",
+    _lib.LOG_REASON_MISSING_START_2: "missing start of fragmented record(2)",
+    _lib.LOG_REASON_IN_MIDDLE: "error in middle of record",
+    _lib.LOG_REASON_UNKNOWN_TYPE: "unknown record type %u",
+}
+LOG_RECORD_DTYPE = np.dtype([("offset", "<u8"), ("payload", "<u8"), ("length", "<u8"), ("fragments", "<u4"),
+                             ("reports_before", "<u4")])
+LOG_REPORT_DTYPE = np.dtype([("bytes", "<u8"), ("reason", "<u4"), ("type", "<u4")])
+
+
+@dataclass
+class LogRead:
+    """What log::Reader::ReadRecord returns over a log image, in reader order:
+    ``records`` (LOG_RECORD_DTYPE; ``reports_before`` interleaves them with
+    the reports), ``reports`` as (bytes, reason text) with the reference's
+    strings, and the records' bytes packed in ``payload`` (bytes, or a CUDA
+    tensor from :func:`log_read_dev`)."""
+    records: np.ndarray
+    reports: List[Tuple[int, str]]
+    payload: object
+
+    def record_bytes(self, k: int) -> bytes:
+        r = self.records[k]
+        part = self.payload[int(r["payload"]):int(r["payload"]) + int(r["length"])]
+        return bytes(part) if isinstance(part, (bytes, bytearray, memoryview)) else part.cpu().numpy().tobytes()
+
+
+def _log_read(read, n: int, make_payload, what: str) -> LogRead:
+    """read(payload_ptr, payload_cap, records, rec_cap, reports, rep_cap, totals) -> rc: the totals first, then
+    one call with exact capacities."""
+    tot = _lib.LogReadTotals()
+    _check(read(None, 0, None, 0, None, 0, ctypes.byref(tot)), what)
+    nrec, nrep, nbytes = tot.n_records, tot.n_reports, tot.payload_bytes
+    records = np.zeros(max(nrec, 1), dtype=LOG_RECORD_DTYPE)
+    reports = np.zeros(max(nrep, 1), dtype=LOG_REPORT_DTYPE)
+    payload, ptr = make_payload(max(nbytes, 1))
+    _check(read(ptr, nbytes, records.ctypes.data, nrec, reports.ctypes.data, nrep, ctypes.byref(tot)), what)
+    texts = [(int(r["bytes"]), LOG_REASON_TEXT[int(r["reason"])].replace("%u", str(int(r["type"]))))
+             for r in reports[:nrep]]
+    return LogRead(records[:nrec], texts, payload[:nbytes])
+
+
+def log_read(image: BytesLike, *, initial_offset: int = 0, checksum: bool = True,
+             host: Optional[bool] = None) -> LogRead:
+    """ReadRecord's logical records and corruption reports over a host log
+    image read from ``initial_offset`` (nvl_log_read: the physical scan of
+    :func:`log_scan` under ``host``, then the record rules)."""
+    ptr, n, _keep = _ro(image)
+
+    def make(nbytes):
+        buf = np.zeros(nbytes, dtype=np.uint8)
+        return buf, buf.ctypes.data
+
+    got = _log_read(lambda p, pc, r, rc_, q, qc, t: _lib.lib.nvl_log_read(ptr, n, initial_offset, int(checksum), p, pc,
+                                                                       r, rc_, q, qc, t, _flags(host)),
+                    n, make, "log_read")
+    got.payload = got.payload.tobytes()
+    return got
+
+
+def log_read_dev(image, *, initial_offset: int = 0, checksum: bool = True, stream=None) -> LogRead:
+    """log_read for a log image already in device memory: a contiguous 1-D
+    uint8 torch tensor on the GPU (nvl_log_read_dev: scanned, joined and
+    gathered there).  ``payload`` is a tensor on the image's device."""
+    import torch
+    if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.uint8 and image.dim() == 1
+            and image.is_contiguous()):
+        raise TypeError("log_read_dev: a contiguous 1-D uint8 tensor on the GPU")
+    st_ = torch.cuda.current_stream(image.device).cuda_stream if stream is None else stream
+    n = image.numel()
+
+    def make(nbytes):
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
+        return buf, buf.data_ptr()
+
+    with torch.cuda.device(image.device):
+        return _log_read(lambda p, pc, r, rc_, q, qc, t: _lib.lib.nvl_log_read_dev(
+            image.data_ptr(), n, initial_offset, int(checksum), p, pc, r, rc_, q, qc, t, 0, st_), n, make,
+            "log_read_dev")
 
 
 def log_seal(image: Union[bytearray, np.ndarray], header_offsets: Sequence[int], *, host: Optional[bool] = None) -> None:

@@ -17,6 +17,12 @@ host CRC, one JSON line per (operation, size, engine):
                nvl_log_scan_staged and nvl_log_scan (GPU / host CRC) on the same image in
                registered host memory, with the calling thread's CPU seconds per GiB, and
                the parse path beside nvl_crc32c_read_probe (profiles/log_scan_dev.jsonl)
+  log_read     (--log-read 64,1024 only) nvl_log_read_dev (payload in HBM, and NVL_LOG_PAYLOAD_HOST)
+               on an HBM-resident log written as log::Writer fragments it, against nvl_log_scan_dev
+               on the same image and against what a caller had to do before: the image copied to
+               the host, then a shims::LogReader ReadRecord loop with the host CRC; the legs
+               alternate round by round; plus the gather kernel's share beside a plain
+               device-to-device copy of the payload bytes (profiles/log_read_dev.jsonl)
 Sizes: tables of 256 KiB .. 128 MiB (max_file_size is 2 MiB, util/options.cc:24;
 compaction outputs and L0 flushes, db/builder.cc:35-45, db/db_impl.cc:923).
 Wall clock per call (synchronous entry points), median of R calls after 2 warm-ups.
@@ -38,6 +44,9 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--sizes", default="0.25,2,8,32,128", help="table sizes in MiB")
 ap.add_argument("--log-scan", default=None, metavar="MIB,...",
                 help="run only the device log scan legs on sealed logs of these sizes (e.g. 64,1024)")
+ap.add_argument("--log-read", default=None, metavar="MIB,...",
+                help="run only the device log reader legs on written logs of these sizes (e.g. 64,1024)")
+ap.add_argument("--rounds", type=int, default=5, help="--log-read: alternating rounds of all legs")
 ap.add_argument("--log-shapes", default="100B,1KiB,32KiB", help="record shapes of the --log-scan legs")
 a = ap.parse_args()
 out = open(a.out, "w") if a.out else None
@@ -187,6 +196,177 @@ def log_scan_legs(sizes, reps):
             assert L.nvl_crc32c_host_unregister(img.ctypes.data) == 0
             del dimg
 
+
+def written_log(mib, payload, seed=12):
+    """A log of mib MiB as log::Writer lays it out (db/log_writer.cc:36-82):
+    logical records of `payload` bytes back to back, split into FIRST / MIDDLE
+    / LAST fragments at the block ends.  Built as one chunk of up to 64 MiB
+    whose last record ends exactly at the chunk's end, repeated.  Returns
+    (image, logical records, fragments)."""
+    total = int(mib * 2**20)
+    chunk = min(total, 64 << 20)
+    hdr, lens, types = [], [], []
+    pos = nrec = 0
+    while pos < chunk:
+        left = payload
+        if chunk - pos < 2 * (payload + 7 * (payload // 32761 + 2)):  # the chunk's last record: whatever fits
+            left = -1
+        begin = True
+        while True:
+            room = 32768 - pos % 32768
+            if room < 7:
+                pos += room
+                continue
+            if left < 0:  # fill to the end of the chunk, fragment by fragment
+                n = room - 7
+                end = pos + 7 + n >= chunk
+            else:
+                n = min(left, room - 7)
+                left -= n
+                end = left == 0
+            hdr.append(pos)
+            lens.append(n)
+            types.append(1 if begin and end else 2 if begin else 4 if end else 3)
+            pos += 7 + n
+            begin = False
+            if end:
+                break
+        nrec += 1
+    assert pos == chunk, (pos, chunk)
+    reps_ = total // chunk
+    rng = np.random.default_rng(seed)
+    one = rng.integers(0, 256, chunk, dtype=np.uint8)
+    h = np.array(hdr, dtype=np.int64)
+    ln = np.array(lens, dtype=np.int64)
+    one[h + 4] = ln & 0xFF
+    one[h + 5] = ln >> 8
+    one[h + 6] = np.array(types, dtype=np.uint8)
+    # block trailers are zero
+    ends = h + 7 + ln
+    gap = np.nonzero((ends % 32768) > 32768 - 7)[0]
+    for g in gap:
+        one[ends[g]:(ends[g] // 32768 + 1) * 32768] = 0
+    img = np.tile(one, reps_)
+    hh = (np.arange(reps_, dtype=np.uint64)[:, None] * np.uint64(chunk) + h.astype(np.uint64)[None, :]).ravel()
+    rc = L.nvl_log_seal(img.ctypes.data, img.size, hh.ctypes.data, hh.size, GPU)
+    assert rc == 0, rc
+    return img, nrec * reps_, hh.size
+
+
+def log_read_legs(sizes, reps, rounds):
+    """Per image, `rounds` alternating rounds of
+      read_dev       nvl_log_read_dev, payload in HBM
+      read_dev_host  nvl_log_read_dev, NVL_LOG_PAYLOAD_HOST
+      scan_dev       nvl_log_scan_dev (the parent's code: the difference is the record pass and the gather)
+      copy_then_host the image copied to the host, then shims::LogReader's ReadRecord loop, NVL_FRAMING_HOST
+                     (the parent's code: what a caller of an HBM-resident log had to do)
+    each timed as the median of `reps` calls; then the median and the spread of the rounds' medians.  Then the
+    gather against a device-to-device copy of the same bytes (HIP events)."""
+    import subprocess
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.run(["make", "-s", "-C", native, "-f", "log_read.mk", "liblog_read_harness.so"], check=True)
+    H = ctypes.CDLL(os.path.join(native, "liblog_read_harness.so"))
+    H.shim_log_read_count.restype = ctypes.c_int
+    H.shim_log_read_count.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p]
+    for mib in sizes:
+        for payload, shape in ((100, "100B"), (1024, "1KiB"), (100 * 1024, "32KiB")):
+            if shape not in a.log_shapes.split(","):
+                continue
+            img, nrec, nfrag = written_log(mib, payload)
+            nbytes = img.size
+            gib = nbytes / 2**30
+            dimg = torch.from_numpy(img).to("cuda")
+            tot = _lib.LogReadTotals()
+            assert L.nvl_log_read_dev(dimg.data_ptr(), nbytes, 0, 1, None, 0, None, 0, None, 0, ctypes.byref(tot), 0,
+                                      sptr) == 0
+            assert (tot.n_records, tot.n_reports) == (nrec, 0), (tot.n_records, tot.n_reports, nrec)
+            pbytes = tot.payload_bytes
+            base = {"log_bytes": nbytes, "records": nrec, "fragments": nfrag, "payload_bytes": pbytes, "shape": shape,
+                    "op": "log_read"}
+            rec = (_lib.LogRecord * nrec)()
+            rp = (_lib.LogReport * 1)()
+            dpay = torch.empty(pbytes, dtype=torch.uint8, device="cuda")
+            hpay = np.empty(pbytes, dtype=np.uint8)
+            himg = np.empty(nbytes, dtype=np.uint8)
+            cap = nfrag + nbytes // 32768 + 4
+            ev = (_lib.LogEvent * cap)()
+            n = ctypes.c_size_t(0)
+            cr, cb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            torch.cuda.synchronize()
+
+            def read_dev():
+                assert L.nvl_log_read_dev(dimg.data_ptr(), nbytes, 0, 1, dpay.data_ptr(), pbytes, rec, nrec, rp, 1,
+                                          ctypes.byref(tot), 0, sptr) == 0
+
+            def read_dev_host():
+                assert L.nvl_log_read_dev(dimg.data_ptr(), nbytes, 0, 1, hpay.ctypes.data, pbytes, rec, nrec, rp, 1,
+                                          ctypes.byref(tot), _lib.LOG_PAYLOAD_HOST, sptr) == 0
+
+            def scan_dev():
+                assert L.nvl_log_scan_dev(dimg.data_ptr(), nbytes, 0, 1, ev, cap, ctypes.byref(n), sptr) == 0
+
+            def copy_then_host():
+                torch.from_numpy(himg).copy_(dimg)
+                assert H.shim_log_read_count(himg.ctypes.data, nbytes, 1, 0, HOST, ctypes.byref(cr),
+                                             ctypes.byref(cb)) == 0
+                assert (cr.value, cb.value) == (nrec, pbytes)
+
+            legs = (("read_dev", read_dev), ("read_dev_host", read_dev_host), ("scan_dev", scan_dev),
+                    ("copy_then_host", copy_then_host))
+            r = reps if mib <= 64 else max(3, reps // 3)
+            meds = {name: [] for name, _ in legs}
+            for rnd in range(rounds):
+                for name, fn in legs:
+                    k = r if name != "copy_then_host" else max(1, r // 3)
+                    fn()
+                    ts = []
+                    for _ in range(k):
+                        t0 = time.perf_counter()
+                        fn()
+                        ts.append(time.perf_counter() - t0)
+                    meds[name].append(float(np.median(ts)))
+                    emit(dict(base, leg=name, round=rnd, ms=round(meds[name][-1] * 1e3, 3), reps=k))
+            assert hpay.tobytes() == dpay.cpu().numpy().tobytes()
+            for name, _ in legs:
+                m = np.array(meds[name])
+                emit(dict(base, leg=name, summary=True, ms=round(float(np.median(m)) * 1e3, 3),
+                          spread_ms=[round(float(m.min()) * 1e3, 3), round(float(m.max()) * 1e3, 3)],
+                          GiBps=round(gib / float(np.median(m)), 2), rounds=rounds))
+            # the gather beside a plain copy of the same bytes: read_dev minus the totals-only call (the scan,
+            # both record scans and the totals round trip, no emit and no gather) bounds emit + gather + D2H of
+            # the records from above; the device-to-device copy of the payload bytes is the floor of a gather
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+            def ev_time(fn, k):
+                fn(); fn()
+                ts = []
+                for _ in range(k):
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                return float(np.median(ts))
+
+            def totals_only():
+                assert L.nvl_log_read_dev(dimg.data_ptr(), nbytes, 0, 1, None, 0, None, 0, None, 0, ctypes.byref(tot),
+                                          0, sptr) == 0
+            src = torch.empty(pbytes, dtype=torch.uint8, device="cuda")
+            t_full, t_tot = ev_time(read_dev, r), ev_time(totals_only, r)
+            t_copy = ev_time(lambda: dpay.copy_(src), r)
+            emit(dict(base, leg="gather_vs_copy", read_dev_event_ms=round(t_full, 3), totals_only_event_ms=round(t_tot, 3),
+                      emit_gather_d2h_ms=round(t_full - t_tot, 3), d2d_copy_ms=round(t_copy, 3),
+                      d2d_copy_GiBps=round(pbytes / 2**30 / (t_copy / 1e3), 1),
+                      gather_bound_GiBps=round(pbytes / 2**30 / (max(t_full - t_tot, 1e-6) / 1e3), 1),
+                      what="emit_gather_d2h_ms = read_dev - totals-only call: the emit kernel, the gather kernel and "
+                           "the copy of the records to the host together; the gather alone is faster than that"))
+            del dimg, dpay, src
+
+
+if a.log_read:
+    log_read_legs([float(x) for x in a.log_read.split(",")], a.reps, a.rounds)
+    sys.exit(0)
 
 if a.log_scan:
     log_scan_legs([float(x) for x in a.log_scan.split(",")], a.reps)
